@@ -9,11 +9,21 @@ same problem at every GPU count (strong scaling). `--n 16384 --nb 512`
 reproduces config 2 (1 GPU).
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29511 bench.py --gpus 8
 
 Every step restores the input matrix (device copy, inside the timed region),
 builds the taskpool and factorizes. Flops = N^3/3 + N^2/2 + N/6.
+
+A plain run sets up, warms up, times the steps and prints the JSON line.
+--full adds the backward-error probe of the last timed factorization (the
+`residual` entry; a run whose residual is too large fails). --dump-outputs DIR
+writes the factor L of the last timed step as DIR/L.npy (float64, N x N, zero
+above the diagonal) or, for a matrix too large for that, DIR/L_sample.npy: a
+fixed seeded sample of entries of the lower triangle. The input is seeded tile
+by tile, so two builds run with the same arguments factor the same matrix.
 """
 import argparse
 import json
@@ -94,6 +104,52 @@ def residual_probe(torch, dist, world, A, store, backup, nb, N, rank, share_gpu)
     return float(torch.linalg.norm(v[:N]) / (torch.sqrt(v[N]) * torch.linalg.norm(x)))
 
 
+DUMP_FULL_MAX_N = 2048      # L.npy up to this order (32 MiB of float64)
+DUMP_SAMPLE = 1 << 22       # entries of L_sample.npy beyond it (32 MiB)
+DUMP_SEED = 20240611
+
+
+def dump_outputs(torch, dist, world, rank, A, store, nb, N, coll_dev, outdir):
+    """The factor the timed path left in `store`, gathered from every rank's
+    tiles: the whole lower triangle for small N, else DUMP_SAMPLE entries (i >= j)
+    drawn by a fixed seed. Entries a rank does not own stay zero and the vectors
+    are summed over ranks; rank 0 writes the file."""
+    import numpy as np
+
+    dev = store.device
+    if N <= DUMP_FULL_MAX_N:
+        ij = torch.tril_indices(N, N)
+        i, j = ij[0], ij[1]
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        a = torch.from_numpy(rng.integers(0, N, DUMP_SAMPLE))
+        b = torch.from_numpy(rng.integers(0, N, DUMP_SAMPLE))
+        i, j = torch.maximum(a, b), torch.minimum(a, b)
+    NT = A.nt
+    li = torch.full((NT, NT), -1, dtype=torch.int64)
+    for n in range(NT):
+        for m in range(n, NT):
+            li[m, n] = A.local_index(m, n)
+    t = li[i // nb, j // nb]
+    own = t >= 0
+    # tiles are column-major: element (r, c) of a tile is at [c][r]
+    flat = (t * nb * nb + (j % nb) * nb + (i % nb))[own].to(dev)
+    vals = torch.zeros(i.numel(), dtype=torch.float64, device=dev)
+    vals[own.to(dev)] = store.view(-1)[flat]
+    vals = vals.to(coll_dev)
+    if world > 1:
+        dist.all_reduce(vals)
+    if rank != 0:
+        return
+    os.makedirs(outdir, exist_ok=True)
+    if N <= DUMP_FULL_MAX_N:
+        L = torch.zeros((N, N), dtype=torch.float64)
+        L[i, j] = vals.cpu()
+        np.save(os.path.join(outdir, "L.npy"), L.numpy())
+    else:
+        np.save(os.path.join(outdir, "L_sample.npy"), vals.cpu().numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -112,7 +168,13 @@ def main():
                     help="multi-rank: accept ranks whose device plane fell back to host staging (default: such a run exits non-zero)")
     ap.add_argument("--device", choices=["gpu", "cpu"], default="gpu",
                     help="cpu: host-resident tiles and CPU task bodies, gloo for the bench's own collectives (tests of the distributed path and its reporting on machines without a GPU; not a measurement)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the backward-error probe of the last timed factorization (the `residual` entry)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the factor of the last one to DIR/L.npy (small N) or a fixed seeded sample of it to DIR/L_sample.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     cpu = args.device == "cpu"
 
     import torch
@@ -281,13 +343,20 @@ def main():
     flops = N ** 3 / 3 + N ** 2 / 2 + N / 6
     gflops = flops / (ms * 1e-3) / 1e9
 
-    # Backward error of the LAST timed factorization over the whole matrix (outside
-    # the timed region): r = ||A x - L (L^T x)|| / (||A||_F ||x||) for a random x,
-    # each rank contributing its local tiles, partial vectors summed over ranks.
-    resid = residual_probe(torch, dist, world, A, store, backup, nb, N, rank, args.share_gpu or cpu)
-    _stage(f"residual {resid:.3e}")
-    if not resid < 1e-12:
-        raise RuntimeError(f"DPOTRF residual {resid:.3e} too large")
+    # --full: backward error of the LAST timed factorization over the whole matrix
+    # (outside the timed region): r = ||A x - L (L^T x)|| / (||A||_F ||x||) for a
+    # random x, each rank contributing its local tiles, partial vectors summed
+    # over ranks.
+    resid = None
+    if args.full:
+        resid = residual_probe(torch, dist, world, A, store, backup, nb, N, rank, args.share_gpu or cpu)
+        _stage(f"residual {resid:.3e}")
+        if not resid < 1e-12:
+            raise RuntimeError(f"DPOTRF residual {resid:.3e} too large")
+
+    if args.dump_outputs:
+        dump_outputs(torch, dist, world, rank, A, store, nb, N, coll_dev, args.dump_outputs)
+        _stage("outputs written")
 
     check = None
     if args.check:
@@ -349,7 +418,8 @@ def main():
     out = dict(base)
     out["value"] = round(gflops, 1)
     out["ms_per_step"] = round(ms, 3)
-    out["residual"] = float(f"{resid:.3e}")
+    if resid is not None:
+        out["residual"] = float(f"{resid:.3e}")
     out["device_plane"] = planes
     if probe is not None:
         out["ipc_probe"] = probe

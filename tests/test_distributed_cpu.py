@@ -215,10 +215,54 @@ def test_bench_json_before_failing_exit(pa):
     assert out["value"] is None and "device plane is not ipc" in out["error"]
     assert [p["plane"] for p in out["device_plane"]] == ["host", "host"]
     assert out["ipc_probe"]["codes"] == [[0, -1], [-1, 0]]
-    outs = _bench_ranks(2, ["--allow-host-plane"])
+    outs = _bench_ranks(2, ["--allow-host-plane", "--full"])
     assert [rc for rc, _, _ in outs] == [0, 0], [(rc, e[-800:]) for rc, _, e in outs]
     out = json.loads([l for l in outs[0][1].splitlines() if l.startswith("{")][-1])
     assert out["value"] > 0 and out["residual"] < 1e-12
     for r, c in enumerate(out["comm"]):
         assert c["get_fragments"] > 0 and sum(c["bytes_from_peer"]) == c["bytes_fragments"], c
         assert c["bytes_from_peer"][r] == 0
+
+
+def test_bench_dump_outputs(pa, tmp_path):
+    """bench.py --dump-outputs: the factor of the last timed step as L.npy
+    (float64, zero above the diagonal), the same matrix from 1 rank and from 2
+    (each rank contributing its tiles), and equal to host LAPACK's factor of
+    the seeded input. Bound: both factorizations are backward stable and the
+    input (random in [-0.5, 0.5) + N*I) has a condition number below 2, so the
+    factors differ by a few n*eps = 768 * 2.2e-16 = 1.7e-13 relative to max|L|;
+    1e-12 leaves a factor 6. A plain run carries no `residual` entry."""
+    import json
+
+    import numpy as np
+    import torch
+
+    N, nb = 768, 128  # the shape _bench_ranks runs
+    NT = N // nb
+    full = torch.zeros((N, N), dtype=torch.float64)
+    gen = torch.Generator()
+    for n in range(NT):
+        for m in range(n, NT):
+            gen.manual_seed(1_000_003 * m + n)
+            t = torch.rand((nb, nb), dtype=torch.float64, generator=gen) - 0.5
+            if m == n:
+                t = (t + t.t()) * 0.5 + N * torch.eye(nb, dtype=torch.float64)
+            full[m * nb:(m + 1) * nb, n * nb:(n + 1) * nb] = t
+    S = torch.tril(full) + torch.tril(full, -1).t()
+    Lref = torch.linalg.cholesky(S).numpy()
+    got = {}
+    for nranks in (1, 2):
+        d = tmp_path / f"r{nranks}"
+        outs = _bench_ranks(nranks, ["--allow-host-plane", "--dump-outputs", str(d)])
+        assert [rc for rc, _, _ in outs] == [0] * nranks, [(rc, e[-800:]) for rc, _, e in outs]
+        out = json.loads([l for l in outs[0][1].splitlines() if l.startswith("{")][-1])
+        assert out["ms_per_step"] > 0 and out["steps"] == 1 and "residual" not in out
+        assert sorted(os.listdir(d)) == ["L.npy"]
+        L = np.load(d / "L.npy")
+        assert L.dtype == np.float64 and L.shape == (N, N)
+        assert not np.triu(L, 1).any()
+        err = np.abs(L - Lref).max() / np.abs(Lref).max()
+        print(f"ranks {nranks}: max |L - Lref| / max |Lref| = {err:.3e}")
+        assert err < 1e-12
+        got[nranks] = L
+    assert np.abs(got[1] - got[2]).max() / np.abs(Lref).max() < 1e-12

@@ -188,7 +188,7 @@ def test_headline_tile_size_8_ranks_shared_gpu(pa, route):
     port = 29600 + (os.getpid() + (7 if route != "gather" else 0)) % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(os.path.dirname(HERE), "bench.py"), "--gpus", "8", "--size", "16384", "--nb", "1024",
-           "--steps", "1", "--warmup", "0", "--share-gpu", "--cores", "1"]
+           "--steps", "1", "--warmup", "0", "--share-gpu", "--cores", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, start_new_session=True, env=dict(os.environ, **ROUTES[route]))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
