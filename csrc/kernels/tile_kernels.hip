@@ -5,6 +5,11 @@
 //    the 256 CUs. Two tilings: 128x128 (4 waves x 64x64, 16 accumulators per wave)
 //    for big batches and 64x64 for small ones. Workgroups are remapped so a task's
 //    tiles stay on one XCD (its operands stay in that XCD's 4 MiB L2).
+//    Two k loops for the full, register-staged, double-buffered launches
+//    (PARSEC_GEMM_MAINLOOP / gemm_mainloop()): 0 = load, multiply, store, barrier
+//    per k-tile; 1 = rotated by one kk-group with the fragments double-buffered
+//    in registers, so MFMAs span the k-tile barrier (default). Same results bit
+//    for bit.
 //  * MFMA operand roles are swapped (A-operand <- B tile, B-operand <- A tile) so
 //    the f64 accumulator layout (col = lane&15, row = (lane>>4)+4*r, measured on
 //    MI355X: profiles/probe_mfma_f64_and_vendor_baselines.log) maps lanes to
@@ -157,10 +162,21 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
 // k-tile's MFMA work instead of in front of it, and the epilogue forms
 // alpha AB + beta C from registers (a pure store). Needs the register budget of
 // two waves per SIMD (launched with one workgroup per CU).
-template <int BM, int BN, int BK, int WM, int WN, bool TRANSA, bool TRANSB, bool FULL, int NBUF, int PF, int EPI, bool DL = false, bool INPL = false>
+// ML = 1 (FULL, !DL, NBUF 2, PF 1, !INPL only): the rotated k loop. The k loop
+// is shifted by one kk-group (4 of k) and the MFMA fragments live in two
+// register sets: the fragments of group g + 1 are read while group g is
+// multiplied, the last group of a k-tile is multiplied behind the k-tile
+// barrier while the first group of the next k-tile is read and the global loads
+// of the one after are issued. The global addresses are a uniform base advanced
+// by a k-tile plus per-thread offsets fixed before the loop (no 64-bit vector
+// multiply per k-tile). Split-K chunks and the a_lower / b_upper K ranges are BK
+// multiples and take the same loop. ML = 0 is the loop every other launch runs.
+template <int BM, int BN, int BK, int WM, int WN, bool TRANSA, bool TRANSB, bool FULL, int NBUF, int PF, int EPI, bool DL = false, bool INPL = false, int ML = 0>
 __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, int ks, int nsplit, double (&As)[NBUF][BK][BM + (((BM % 32) == 16) ? 0 : 16)],
                                           double (&Bs)[NBUF][BK][BN + (((BN % 32) == 16) ? 0 : 16)]) {
   static_assert(PF == 1 || NBUF == 2, "two tiles in flight need the double-buffered LDS");
+  static_assert(ML == 0 || (FULL && !DL && NBUF == 2 && PF == 1 && !INPL), "rotated k loop: full, register-staged, double-buffered tiles only");
+  constexpr bool ROT = ML == 1;
   constexpr int NT = WM * WN * 64;
   constexpr int WTM = BM / WM;
   constexpr int WTN = BN / WN;
@@ -412,7 +428,38 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
       }
     }
   } else {
-  load_tile(0);
+  // ROT: global addresses of the k loop = one uniform base per operand, advanced
+  // by a k-tile per load, plus per-thread element offsets fixed here (the
+  // plain loop recomputes (size_t)gk * lda per load and k-tile)
+  const double* __restrict__ Ak = A;
+  const double* __restrict__ Bk = B;
+  size_t oa[ROT ? A_PAIRS : 1], ob[ROT ? B_PAIRS : 1];
+  if constexpr (ROT) {
+#pragma unroll
+    for (int e = 0; e < A_PAIRS; ++e) {
+      const int idx = tid + NT * e;
+      if (TRANSA) oa[e] = (size_t)(m0 + idx / (BK / 2)) * lda + (idx % (BK / 2)) * 2;
+      else oa[e] = (size_t)(idx / (BM / 2)) * lda + m0 + (idx % (BM / 2)) * 2;
+    }
+#pragma unroll
+    for (int e = 0; e < B_PAIRS; ++e) {
+      const int idx = tid + NT * e;
+      if (TRANSB) ob[e] = (size_t)(idx / (BN / 2)) * ldb + n0 + (idx % (BN / 2)) * 2;
+      else ob[e] = (size_t)(n0 + idx / (BK / 2)) * ldb + (idx % (BK / 2)) * 2;
+    }
+  }
+  const size_t step_a = TRANSA ? (size_t)BK : (size_t)BK * lda, step_b = TRANSB ? (size_t)BK * ldb : (size_t)BK;
+  // loads the next k-tile in line (tiles are taken strictly in order)
+  auto load_next = [&]() {
+#pragma unroll
+    for (int e = 0; e < A_PAIRS; ++e) ra[e] = *reinterpret_cast<const double2_t*>(Ak + oa[ROT ? e : 0]);
+#pragma unroll
+    for (int e = 0; e < B_PAIRS; ++e) rb[e] = *reinterpret_cast<const double2_t*>(Bk + ob[ROT ? e : 0]);
+    Ak += step_a;
+    Bk += step_b;
+  };
+  if constexpr (ROT) load_next();
+  else load_tile(0);
   if (LATE && late) {
 #pragma unroll
     for (int i = 0; i < FN; ++i)
@@ -435,7 +482,83 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
       }
   }
   store_tile(0);
-  if (PF == 2) {
+  if constexpr (ROT) {
+    // Rotated k loop. The fragments of kk-group g + 1 are read into the other
+    // register set while group g is multiplied, and the rotation crosses the
+    // k-tile boundary: the last group of k-tile kt is multiplied BEHIND the
+    // barrier, from registers, while the wave reads group 0 of k-tile kt + 1 and
+    // issues the global loads of k-tile kt + 2 -- the MFMA pipe keeps work over
+    // the store / barrier / load-issue / first-read sequence that every wave of
+    // the workgroup runs at the same moment. Each accumulator still takes its
+    // MFMAs in ascending k order, so the results are those of the loop below bit
+    // for bit.
+    // Two LDS buffers suffice: (1) every read of buffer cur in k-tile kt (groups
+    // 1 .. NKK - 1; group 0 was read behind the previous barrier) is issued and
+    // waited for before the barrier of kt (__syncthreads drains lgkmcnt), and
+    // the next writes to cur (k-tile kt + 2) come behind that barrier; (2) the
+    // writes of k-tile kt + 1 to cur ^ 1 come behind the barrier of kt - 1, after
+    // which nobody reads cur ^ 1 (its last reads were k-tile kt - 1's, before that
+    // barrier), and complete before the barrier of kt; its first reads (kt + 1,
+    // group 0) come behind it. ra / rb are free for the loads of kt + 2 because
+    // the store of kt + 1 precedes the barrier.
+    constexpr int NKK = BK / 4;
+    static_assert(NKK % 2 == 0, "group 0 of every k-tile lives in register set 0");
+    double bfr[2][FM], afr[2][FN];
+    auto read_frag = [&](int buf, int kk, double* bf, double* af) {
+#pragma unroll
+      for (int j = 0; j < FM; ++j) bf[j] = KA ? a_km(buf)[(wm * WTM + j * 16 + fr) * KS + kk + fk] : As[buf][kk + fk][wm * WTM + j * 16 + fr];
+#pragma unroll
+      for (int i = 0; i < FN; ++i) af[i] = KB ? b_km(buf)[(wn * WTN + i * 16 + fr) * KS + kk + fk] : Bs[buf][kk + fk][wn * WTN + i * 16 + fr];
+    };
+    __syncthreads();
+    read_frag(0, 0, bfr[0], afr[0]);
+    if (1 < nkt) load_next();
+    // one k-tile; more: k-tile kt + 1 exists (store it, barrier, read its group
+    // 0), load: k-tile kt + 2 exists (issue its global loads). Both are constants
+    // at the three call sites, so the steady-state body is straight-line code and
+    // the compiler's wait counts are exact (a branch that skips the store or the
+    // read makes it wait for every LDS operation at the join, i.e. for the fresh
+    // reads in front of the held-back MFMAs).
+    auto k_tile = [&](int cur, bool more, bool load) {
+      if (args.yield && tid < 64) {
+        // wave 0 sleeps while this CU hosts critical work; the other waves wait
+        // for it at the k-tile barrier
+        int polls = 0;
+        while (crit_count(ykey) > 0 && polls++ < kYieldMaxPolls) __builtin_amdgcn_s_sleep(4);
+      }
+#pragma unroll
+      for (int g = 0; g < NKK; ++g) {
+        if (g + 1 < NKK) {
+          if (g == NKK - 2 && more) store_tile(cur ^ 1);  // k-tile kt + 1, loaded a k-tile ago
+          read_frag(cur, (g + 1) * 4, bfr[(g + 1) & 1], afr[(g + 1) & 1]);
+        } else if (more) {
+          // only the last group is held back: without this fence the compiler also
+          // moves group NKK - 2 behind the barrier (a third fragment set: 128 VGPRs
+          // and spills in sibling instantiations) and leaves the store and the reads
+          // in front of it with no MFMA of this wave to cover their latency. Inside
+          // the two regions the compiler's own order stays: a fence around every
+          // group (reads strictly in front of the MFMAs that cover them) measured
+          // +3.0 .. 3.9 % over the plain loop where this form gives +5.1 .. 5.6 %
+          // (profiles/gemm_rotated_mainloop.txt)
+          __builtin_amdgcn_sched_barrier(0);
+          __syncthreads();
+          read_frag(cur ^ 1, 0, bfr[0], afr[0]);
+          if (load) load_next();
+        }
+#pragma unroll
+        for (int i = 0; i < FN; ++i)
+#pragma unroll
+          for (int j = 0; j < FM; ++j) acc[i][j] = __builtin_amdgcn_mfma_f64_16x16x4f64(afr[g & 1][i], bfr[g & 1][j], acc[i][j], 0, 0, 0);
+      }
+    };
+    int kt = 0;
+    for (; kt + 2 < nkt; ++kt) k_tile(kt & 1, true, true);
+    if (kt + 1 < nkt) {
+      k_tile(kt & 1, true, false);
+      ++kt;
+    }
+    k_tile(kt & 1, false, false);
+  } else if (PF == 2) {
     // slot 1 (ra/rb) carries the odd tiles, slot 2 (ra2/rb2) the even ones
     if (1 < nkt) load_tile_to(BK, ra, rb);
     if (2 < nkt) load_tile_to(2 * BK, ra2, rb2);
@@ -518,7 +641,7 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
   crit_release(args.claim);
 }
 
-template <int BM, int BN, int BK, int WM, int WN, bool TRANSA, bool TRANSB, bool FULL, int NBUF = 2, int OCC = WM * WN / 2, int PF = 1, int EPI = 0, bool DL = false, bool INPL = false>
+template <int BM, int BN, int BK, int WM, int WN, bool TRANSA, bool TRANSB, bool FULL, int NBUF = 2, int OCC = WM * WN / 2, int PF = 1, int EPI = 0, bool DL = false, bool INPL = false, int ML = 0>
 __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(OCC))) void dgemm_batch_kernel(const GemmBatchArgs args) {
   constexpr int PADM = ((BM % 32) == 16) ? 0 : 16;
   constexpr int PADN = ((BN % 32) == 16) ? 0 : 16;
@@ -556,7 +679,7 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(OC
     ks = u % nsplit;
   }
   if (tile >= args.total_tiles) return;
-  gemm_tile<BM, BN, BK, WM, WN, TRANSA, TRANSB, FULL, NBUF, PF, EPI, DL, INPL>(args, tile, ks, nsplit, As, Bs);
+  gemm_tile<BM, BN, BK, WM, WN, TRANSA, TRANSB, FULL, NBUF, PF, EPI, DL, INPL, ML>(args, tile, ks, nsplit, As, Bs);
 }
 
 // Persistent form: a grid of (at most) one round of resident workgroups walks
@@ -896,6 +1019,7 @@ static int g_gemm_variant = -1;      // big-tile kernel shape (PARSEC_GEMM_VARIA
 static int g_gemm_full = -1;         // PARSEC_GEMM_FULL=0 disables the unchecked fast path
 static int g_gemm_big_tiles = 384;   // PARSEC_GEMM_BIG_TILES: 128x128 tiles in a launch to pick the big kernel
 static int g_gemm_splitk = -1;       // PARSEC_GEMM_SPLITK=0 disables the split-K tail of the 128x128 kernel
+static int g_gemm_mainloop = -1;     // PARSEC_GEMM_MAINLOOP: k loop of the full register-staged launches, 0 plain, 1 rotated (default)
 static int g_gemm_slots = 512;       // resident 128x128 workgroups (2 per CU): one round of the big kernel
 static int g_gemm_chunk_fill = -1;   // PARSEC_GEMM_CHUNK_FILL=0: fixed 40-descriptor launches
 // resident 128x128 workgroups of the launch being issued: half when bulk
@@ -979,6 +1103,8 @@ static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hi
   // direct-to-LDS k-tiles for the NT bulk GEMM (PARSEC_GEMM_DLDS=1; off until measured)
   static const int dl_env = getenv("PARSEC_GEMM_DLDS") ? atoi(getenv("PARSEC_GEMM_DLDS")) : 0;
   const bool dl = dl_env != 0 && !late && a.stagger == 0;
+  // rotated k loop (gemm_tile ML = 1) for the full, register-staged, double-buffered launches
+  const bool rot = g_gemm_mainloop == 1;
   if (persist) {
     a.main_tiles = total;
     a.ksplit = 1;
@@ -999,6 +1125,11 @@ static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hi
         hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E, true>), grid, block, pad, stream, a);     \
         break;                                                                                                                               \
       }                                                                                                                                      \
+    if constexpr (NBUF == 2 && PF == 1)                                                                                                      \
+      if (rot && full && !persist) {                                                                                                         \
+        hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E, false, false, 1>), grid, block, pad, stream, a); \
+        break;                                                                                                                               \
+      }                                                                                                                                      \
     if (persist) hipLaunchKernelGGL((dgemm_persist_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E>), grid, block, pad, stream, a);  \
     else if (full) hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E>), grid, block, pad, stream, a);  \
     else hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, false, NBUF, OCC, PF, 0>), grid, block, pad, stream, a);          \
@@ -1007,6 +1138,11 @@ static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hi
   do {                                                                                                              \
     if constexpr (BM == 128) {                                                                                      \
       if (late && !persist) {                                                                                       \
+        if constexpr (NBUF == 2 && PF == 1)                                                                         \
+          if (rot) {                                                                                                \
+            hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, 2, PF, 2, false, false, 1>), grid, block, pad, stream, a); \
+            break;                                                                                                  \
+          }                                                                                                         \
         hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, 2, PF, 2>), grid, block, pad, stream, a); \
         break;                                                                                                      \
       }                                                                                                             \
@@ -1046,6 +1182,8 @@ static void gemm_policy_init() {
     int dev = 0, ncu = 0;
     if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0)
       g_gemm_slots = 2 * ncu;
+    e = getenv("PARSEC_GEMM_MAINLOOP");
+    g_gemm_mainloop = e ? (atoi(e) == 0 ? 0 : 1) : 1;  // measured: profiles/gemm_rotated_mainloop.txt, tests/test_gemm_mainloop_gpu.py
     e = getenv("PARSEC_GEMM_CHUNK_FILL");
     g_gemm_chunk_fill = e ? atoi(e) : 1;
     e = getenv("PARSEC_GEMM_SLOTS");
@@ -1058,6 +1196,14 @@ int gemm_splitk(int on) {
   gemm_policy_init();
   const int prev = g_gemm_splitk;
   if (on >= 0) g_gemm_splitk = on;
+  return prev;
+}
+
+// k loop of the full register-staged GEMM launches: 0 plain, 1 rotated, < 0 queries; returns the previous setting.
+int gemm_mainloop(int mode) {
+  gemm_policy_init();
+  const int prev = g_gemm_mainloop;
+  if (mode >= 0) g_gemm_mainloop = mode == 0 ? 0 : 1;
   return prev;
 }
 
@@ -2882,6 +3028,7 @@ void* test_ws(size_t bytes) {
 extern "C" {
 int parsec_amd_gemm_tile_policy(int p) { return parsec::kern::gemm_tile_policy(p); }
 int parsec_amd_gemm_splitk(int on) { return parsec::kern::gemm_splitk(on); }
+int parsec_amd_gemm_mainloop(int mode) { return parsec::kern::gemm_mainloop(mode); }
 int parsec_amd_dgemm_batch(const parsec::GemmDesc* descs, int n, void* stream) {
   // PARSEC_GEMM_PAD_TEST=1: launch like a DPOTRF bulk stream (padded LDS: one
   // 128x128 workgroup per CU) -- kernel benchmarks of the in-DAG regime

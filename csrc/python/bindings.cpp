@@ -26,6 +26,7 @@ using namespace parsec;
 extern "C" int parsec_amd_dgemm_batch(const GemmDesc* descs, int n, void* stream);
 extern "C" int parsec_amd_gemm_tile_policy(int p);
 extern "C" int parsec_amd_gemm_splitk(int on);
+extern "C" int parsec_amd_gemm_mainloop(int mode);
 extern "C" int parsec_amd_potrf_steps(int on);
 extern "C" int parsec_amd_potrf_stamps(long long* out);
 extern "C" int parsec_amd_dtrsm_batch(const TrsmDesc* descs, int n, void* stream);
@@ -698,6 +699,7 @@ PYBIND11_MODULE(_C, m) {
   });
   m.def("kernel_gemm_tile_policy", [](int p) { return parsec_amd_gemm_tile_policy(p); });
   m.def("kernel_gemm_splitk", [](int on) { return parsec_amd_gemm_splitk(on); }, "split-K tail of the 128x128 grouped DGEMM: 1 on, 0 off, -1 query; returns the previous setting");
+  m.def("kernel_gemm_mainloop", [](int mode) { return parsec_amd_gemm_mainloop(mode); }, "k loop of the full register-staged grouped DGEMM: 0 plain, 1 rotated, -1 query; returns the previous setting");
   m.def("cpu_capability", []() {
     const CpuCapability c = cpu_capability();
     py::dict d;
