@@ -7,12 +7,17 @@
            GPU bodies, Gpoint-updates/s and GFLOP/s at 8 flop/point (config 5)
   dtd_gemm DTD tiled DGEMM C += A B on 4 x 4 tiles, CPU bodies in one process
            (config 1, the plumbing check), GFLOP/s
+  potrs    solve with the Cholesky factor (DPOTRS = the two dtrsm_LL.jdf sweeps):
+           A factored once outside the timed region, every timed step restores B
+           and solves, GFLOP/s with 2 N^2 NRHS; the same process then times
+           torch.cholesky_solve on the dense factor (what a user does without it)
 
 Multi-GPU: launch like bench.py (torch.distributed.run, one rank per GPU).
 
     python benchmarks/bench_workloads.py qr --n 16384 --nb 512
     python benchmarks/bench_workloads.py stencil --n 512 --b 128 --iters 20
     python benchmarks/bench_workloads.py dtd_gemm --n 2048
+    python benchmarks/bench_workloads.py potrs --n 16384 --nb 512 --nrhs 16384
 """
 import argparse
 import json
@@ -241,12 +246,108 @@ def bench_dtd_gemm(args):
     return out, 0
 
 
+def bench_potrs(args):
+    import torch
+
+    import parsec_amd as pa
+
+    world, rank, local = _dist()
+    if world > 1:
+        raise RuntimeError("potrs: one GPU (the yardstick is a single-device torch.cholesky_solve)")
+    if not torch.cuda.is_available():
+        raise RuntimeError("potrs: no GPU")
+    N, nb, NRHS = args.n, args.nb, args.nrhs
+    nbr = args.nbr or min(nb, NRHS)
+    dev = torch.device("cuda", 0)
+    ctx = pa.init(args.cores)
+    gpu = pa.first_gpu_device_index()
+    if gpu < 0:
+        raise RuntimeError("no GPU device registered in the runtime")
+    NT, NTB = -(-N // nb), -(-NRHS // nbr)
+
+    def run(tp):
+        ctx.add_taskpool(tp)
+        ctx.start()
+        ctx.wait()
+
+    def dense_of(store, rows, cols, mb, cb):  # a dense COPY of a tiled store [n][m][col][row]
+        return store.permute(1, 3, 0, 2).reshape(store.shape[1] * mb, store.shape[0] * cb)[:rows, :cols].contiguous()
+
+    # SPD input as in bench.py (random symmetric, diagonally dominant), factored once
+    sa = torch.zeros((NT, NT, nb, nb), dtype=torch.float64, device=dev)
+    A = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nb, N, N, device=gpu, ptr=sa.data_ptr())
+    gen = torch.Generator(device=dev).manual_seed(12345)
+    R = torch.rand((N, N), dtype=torch.float64, device=dev, generator=gen) - 0.5
+    S = (R + R.t()) * 0.5 + N * torch.eye(N, dtype=torch.float64, device=dev)
+    del R
+    pad = torch.zeros((NT * nb, NT * nb), dtype=torch.float64, device=dev)
+    pad[:N, :N] = S
+    sa.copy_(pad.reshape(NT, nb, NT, nb).permute(2, 0, 3, 1))
+    del pad
+    torch.cuda.synchronize()
+    tp, info = pa.dpotrf_jdf_new(A)
+    run(tp)
+    if pa.read_int(info) != 0:
+        raise RuntimeError("dpotrf reported a non-SPD matrix")
+    sb = torch.zeros((NTB, NT, nbr, nb), dtype=torch.float64, device=dev)
+    B = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nbr, N, NRHS, device=gpu, ptr=sb.data_ptr())
+    B0 = torch.rand((N, NRHS), dtype=torch.float64, device=dev, generator=gen) - 0.5
+    pad = torch.zeros((NT * nb, NTB * nbr), dtype=torch.float64, device=dev)
+    pad[:N, :NRHS] = B0
+    backup = pad.reshape(NT, nb, NTB, nbr).permute(2, 0, 3, 1).contiguous()
+    del pad
+    torch.cuda.synchronize()
+
+    def step():
+        sb.copy_(backup)
+        torch.cuda.synchronize()
+        tp = pa.dpotrs_new(pa.MATRIX_LOWER, A, B)
+        run(tp)
+        pa.taskpool_free(tp)
+
+    for _ in range(args.warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / args.steps
+    flops = 2.0 * N * N * NRHS
+    X = dense_of(sb, N, NRHS, nb, nbr)
+    resid = float(torch.linalg.norm(S @ X - B0) / (torch.linalg.norm(S) * torch.linalg.norm(X) + torch.linalg.norm(B0)))
+    if not resid < 1e-13:
+        raise RuntimeError(f"DPOTRS backward error {resid:.3e} too large")
+    # yardstick: the dense factor gathered from the tiles, torch.cholesky_solve
+    # (out of place, so it needs no restore), same warm-up and repeats
+    L = torch.tril(dense_of(sa, N, N, nb, nb))
+    for _ in range(max(1, args.warmup)):
+        Y = torch.cholesky_solve(B0, L)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        Y = torch.cholesky_solve(B0, L)
+    torch.cuda.synchronize()
+    dty = (time.perf_counter() - t0) / args.steps
+    diff = float(torch.linalg.norm(X - Y) / torch.linalg.norm(Y))
+    ctx.fini()
+    out = {"metric": "GFLOP/s DPOTRS (dtrsm_LL.jdf, HBM-resident tiles, B restored every step)", "value": round(flops / dt / 1e9, 1), "unit": "GFLOP/s",
+           "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "dtype": "fp64",
+           "backward_error": resid, "yardstick": "torch.cholesky_solve on the dense factor, same process",
+           "yardstick_gflops": round(flops / dty / 1e9, 1), "yardstick_ms": round(dty * 1e3, 3), "ratio_to_yardstick": round(dty / dt, 3),
+           "rel_diff_to_yardstick": diff,
+           "config": {"model": "DPOTRS", "N": N, "nb": nb, "NRHS": NRHS, "nbr": nbr, "cores": args.cores}}
+    return out, 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm"])
+    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm", "potrs"])
     ap.add_argument("--n", "--size", dest="n", type=int, default=None, help="matrix order (use --size under torchrun)")
     ap.add_argument("--nb", type=int, default=512)
     ap.add_argument("--ib", type=int, default=32, help="qr: accepted for the reference's command line; both taskpools factor 32-column sub-panels (qr_sub2c) and apply one nb x nb block reflector per tile")
+    ap.add_argument("--nrhs", type=int, default=None, help="potrs: right-hand sides (default: n)")
+    ap.add_argument("--nbr", type=int, default=0, help="potrs: tile width of B (default: min(nb, nrhs))")
     ap.add_argument("--b", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=2)
@@ -261,8 +362,10 @@ def main():
                     help="qr: rows per TS domain of the hierarchical tree (0: one flat TS chain per process row, TT binary tree across process rows; 1 GPU measured fastest flat: profiles/r3_qr_tree_ab.jsonl)")
     args = ap.parse_args()
     if args.n is None:
-        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048}[args.workload]
-    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm}[args.workload]
+        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048, "potrs": 16384}[args.workload]
+    if args.nrhs is None:
+        args.nrhs = args.n
+    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm, "potrs": bench_potrs}[args.workload]
     out, rank = fn(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -17,6 +17,21 @@ ptg::PtgTaskpool* dpotrf_new(TiledMatrix* A, int uplo, int* info_host);
 // parsec-ptgpp at build time (lower only, W = L^-1 panel solves).
 ptg::PtgTaskpool* dpotrf_jdf_new(TiledMatrix* A, int* info_host);
 int dpotrf_fuse_syrk(int set);  // SYRK(k-1,k) fused into POTRF(k) in new dpotrf_L.jdf taskpools; set < 0 queries
+// Tiled triangular solve B := alpha op(A)^-1 B from the JDF source
+// algos/jdf/dtrsm_LL.jdf: side Left, uplo Lower, trans NoTrans or Trans, diag
+// NonUnit (MatrixSide / MatrixUplo / MatrixTrans / MatrixDiag). A is N x N with
+// square tiles, B is N x NRHS with B->mb == A->nb; A and B may be distributed
+// differently. Any other request returns nullptr after a warning.
+ptg::PtgTaskpool* dtrsm_new(int side, int uplo, int trans, int diag, double alpha, TiledMatrix* A, TiledMatrix* B);
+// Solve A X = B with the Cholesky factor L that dpotrf left in A (lower only):
+// the L sweep composed with the L^T sweep. B is overwritten with X. Freeing the
+// returned taskpool (taskpool_free) frees the two sweeps.
+Taskpool* dpotrs_new(int uplo, TiledMatrix* A, TiledMatrix* B);
+// dpotrf_jdf_new composed with dpotrs_new. When the factorization fails
+// (*info != 0 once it completed) the solve taskpools start empty: B is left
+// untouched. One rank only (nullptr otherwise): ranks see only the pivots of
+// their own diagonal tiles.
+Taskpool* dposv_new(int uplo, TiledMatrix* A, TiledMatrix* B, int* info);
 // Tiled GEMM C = alpha op(A) op(B) + beta C (PTG; B transposed if transB).
 ptg::PtgTaskpool* dgemm_new(double alpha, TiledMatrix* A, TiledMatrix* B, double beta, TiledMatrix* C, int transB);
 // Tiled QR A = QR (Householder, tile algorithm GEQRT/TSQRT/UNMQR/TSMQR). T holds

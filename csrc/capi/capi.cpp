@@ -1119,6 +1119,16 @@ parsec_taskpool_t* parsec_dpotrf_New(parsec_matrix_uplo_t uplo, parsec_tiled_mat
   if (A->mtype != PARSEC_MATRIX_DOUBLE) fatal("parsec_dpotrf_New: the matrix must hold doubles");
   return algos::dpotrf_jdf_new(tm_of(A), info);
 }
+parsec_taskpool_t* parsec_dtrsm_New(parsec_matrix_side_t side, parsec_matrix_uplo_t uplo, parsec_matrix_trans_t trans, parsec_matrix_diag_t diag,
+                                    double alpha, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B) {
+  return algos::dtrsm_new((int)side, (int)uplo, (int)trans, (int)diag, alpha, tm_of(A), tm_of(B));
+}
+parsec_taskpool_t* parsec_dpotrs_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B) {
+  return algos::dpotrs_new((int)uplo, tm_of(A), tm_of(B));
+}
+parsec_taskpool_t* parsec_dposv_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info) {
+  return algos::dposv_new((int)uplo, tm_of(A), tm_of(B), info);
+}
 int parsec_apply(parsec_context_t* parsec, parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_unary_op_t operation, void* op_args) {
   parsec_taskpool_t* tp = parsec_apply_New(uplo, A, operation, op_args);
   parsec_context_add_taskpool(parsec, tp);

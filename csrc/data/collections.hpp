@@ -19,6 +19,10 @@ namespace parsec {
 
 enum MatrixType : int { MATRIX_BYTE = 0, MATRIX_INTEGER, MATRIX_FLOAT, MATRIX_DOUBLE, MATRIX_COMPLEX_FLOAT, MATRIX_COMPLEX_DOUBLE };
 enum MatrixUplo : int { MATRIX_FULL = 0, MATRIX_LOWER, MATRIX_UPPER };
+// BLAS-style operation selectors of the linear-algebra taskpools (the values DPLASMA / PLASMA use)
+enum MatrixTrans : int { MATRIX_NOTRANS = 111, MATRIX_TRANS = 112, MATRIX_CONJTRANS = 113 };
+enum MatrixDiag : int { MATRIX_NONUNIT = 131, MATRIX_UNIT = 132 };
+enum MatrixSide : int { MATRIX_LEFT = 141, MATRIX_RIGHT = 142 };
 size_t matrix_type_size(int mtype);
 
 struct TiledMatrix : DataCollection {

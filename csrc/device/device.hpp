@@ -127,6 +127,17 @@ struct TrsmDesc {  // B := B * op(L)^-1 ; right side, lower, (trans), non-unit
   const double* invD = nullptr;  // optional: inverses of L's 64x64 diagonal blocks (from POTRF)
   const double* gate_slot = nullptr;  // gate: max|L|, max|W| of the panel (workspace)
 };
+// B := alpha * op(L)^-1 B ; left side, lower, non-unit. L is n x n column-major
+// (only its lower triangle is used), B is n x nrhs.
+struct TrsmLeftDesc {
+  const double* L;
+  double* B;
+  int n, nrhs;
+  int ldl, ldb;
+  double alpha;
+  uint8_t trans;  // 0: L^-1 B (forward sweep), 1: L^-T B (backward sweep)
+  const double* invD;  // optional: inverses of L's 64x64 diagonal blocks, contiguous 4096-double blocks (dtrtri_diag_kernel)
+};
 static_assert(sizeof(GemmDesc) == 96, "GemmDesc grew: the grouped-GEMM kernel argument block is sized for 40 of them");
 
 struct PotrfDesc {
@@ -164,6 +175,9 @@ struct TrsmGemmDesc {
 int trsm_inverse_mode(int mode, double limit);
 double trsm_inverse_limit();
 namespace kern {
+// Inverses of the 64 x 64 diagonal blocks of L (n x n lower, ld ldl) into invD:
+// block b at invD + b * 4096, column-major, padded with the identity
+void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream);
 // device_hip_cu_yield as the kernels see it (QR sub-panel kernels claim their CUs when > 0)
 void set_cu_yield_mode(int m);
 int cu_yield_mode();
@@ -237,6 +251,7 @@ struct KernelBatch {
   std::vector<GemmDesc> pre_gemm;  // launched before everything else (a POTRF's fused last update)
   std::vector<GemmDesc> gemm;
   std::vector<TrsmDesc> trsm;
+  std::vector<TrsmLeftDesc> trsm_left;
   std::vector<PotrfDesc> potrf;
   std::vector<TrsmGemmDesc> trsm_w;
   std::vector<StencilDesc> stencil;
@@ -250,8 +265,8 @@ struct KernelBatch {
   // (kernels: g_crit_cu, bulk_yield) so the chain runs at idle speed
   int claim_cus = 0;  // 1: tile-POTRF steps claim, 2: every kernel of the launch
   bool bulk_yield = false;  // bulk launch: poll the claims
-  bool empty() const { return pre_gemm.empty() && gemm.empty() && trsm.empty() && potrf.empty() && trsm_w.empty() && stencil.empty() && qr_panel.empty() && qr_apply.empty() && generic.empty(); }
-  void clear() { pre_gemm.clear(); gemm.clear(); trsm.clear(); potrf.clear(); trsm_w.clear(); stencil.clear(); qr_panel.clear(); qr_apply.clear(); generic.clear(); }
+  bool empty() const { return pre_gemm.empty() && gemm.empty() && trsm.empty() && trsm_left.empty() && potrf.empty() && trsm_w.empty() && stencil.empty() && qr_panel.empty() && qr_apply.empty() && generic.empty(); }
+  void clear() { pre_gemm.clear(); gemm.clear(); trsm.clear(); trsm_left.clear(); potrf.clear(); trsm_w.clear(); stencil.clear(); qr_panel.clear(); qr_apply.clear(); generic.clear(); }
 };
 
 struct HipDevice;

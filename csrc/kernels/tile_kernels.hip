@@ -1013,6 +1013,133 @@ __global__ __launch_bounds__(kTrsmThreads) void dtrsm_inv_kernel(const TrsmInvAr
   }
 }
 
+// ======================================================== TRSM (left side)
+constexpr int kMaxTrsmLeftBatch = 64;
+struct TrsmLeftArgs {
+  int count;
+  int prio;
+  int block_start[kMaxTrsmLeftBatch + 1];
+  TrsmLeftDesc d[kMaxTrsmLeftBatch];  // invD always set (the launcher fills it in)
+};
+static_assert(sizeof(TrsmLeftArgs) <= 4096, "TrsmLeftArgs exceeds the kernel argument limit");
+
+// B := alpha op(L)^-1 B by 64-row blocks, the scheme of dtrsm_inv_kernel turned
+// on its side. Forward (trans 0): R_j = B_j - L_j,<j X_<j, X_j = invD_j R_j;
+// backward (trans 1, j descending): R_j = B_j - L_>j,j^T X_>j, X_j = invD_j^T R_j.
+// A workgroup owns 16 columns of B for the whole sweep: the strip lives in LDS
+// as [row][16] (stride 16: conflict-free MFMA B-operand reads), its rows padded
+// with zeros to a multiple of 64, so the MFMA loops carry no masks: a lane whose
+// L row / column lies past n reads the last valid one instead (finite data times
+// the zero padding, or a result row that is written back as zero). 8 waves: wave
+// (g, h) computes rows 16g..16g+15 of the block over half h of the reduction.
+__global__ __launch_bounds__(kTrsmThreads) void dtrsm_left_kernel(const TrsmLeftArgs args) {
+  extern __shared__ double P[];  // [rows padded][16], then red[16][64]
+  PARSEC_WAVE_PRIO(args.prio);
+  const int b = blockIdx.x;
+  const int di = find_desc(args, args.block_start, b);
+  const TrsmLeftDesc& d = args.d[di];
+  const int j0 = (b - args.block_start[di]) * 16;
+  const int n = d.n, nrhs = d.nrhs;
+  const int nblk = (n + 63) / 64;
+  const int np = nblk * 64;
+  double* red = P + np * 16;
+  const bool tr = d.trans != 0;
+  const double alpha = d.alpha;
+  double* Bp = d.B;
+  const size_t ldb = d.ldb;
+  const double* __restrict__ L = d.L;
+  const size_t ldl = d.ldl;
+  const double* __restrict__ invD = d.invD;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int g = wv & 3, h = wv >> 2;
+  const int fr = lane & 15, fk = lane >> 4;
+  for (int idx = tid; idx < np * 16; idx += kTrsmThreads) {
+    const int i = idx >> 4, jj = idx & 15;
+    P[idx] = (i < n && j0 + jj < nrhs && alpha != 0.0) ? alpha * Bp[(size_t)(j0 + jj) * ldb + i] : 0.0;
+  }
+  __syncthreads();
+  for (int s = 0; s < nblk; ++s) {
+    const int jb = tr ? nblk - 1 - s : s;
+    const int c0 = jb * 64;
+    const int cw = min(c0 + 16 * g + fr, n - 1);  // L row (forward) / column (backward) this lane feeds as the MFMA A-operand
+    double4_t acc[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    if (!tr) {
+      const double* __restrict__ Lp = L + cw;
+      const int kh = c0 / 2;  // multiple of 32
+      const int kbeg = h * kh, kend = kbeg + kh;
+      for (int k = kbeg; k < kend; k += 16) {
+        double av[4], bv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          av[u] = Lp[(size_t)(k + 4 * u + fk) * ldl];
+          bv[u] = P[(k + 4 * u + fk) * 16 + fr];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc[u], 0, 0, 0);
+      }
+    } else {
+      const double* __restrict__ Lp = L + (size_t)cw * ldl;
+      const int kh = (np - c0 - 64) / 2;  // multiple of 32
+      const int kbeg = c0 + 64 + h * kh, kend = kbeg + kh;
+      for (int k = kbeg; k < kend; k += 16) {
+        double av[4], bv[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          av[u] = Lp[min(k + 4 * u + fk, n - 1)];  // rows >= n meet the strip's zero padding
+          bv[u] = P[(k + 4 * u + fk) * 16 + fr];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc[u], 0, 0, 0);
+      }
+    }
+    double4_t sum = acc[0] + acc[1] + acc[2] + acc[3];
+    if (h == 1) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) red[(g * 4 + q) * 64 + lane] = sum[q];
+    }
+    __syncthreads();
+    if (h == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = c0 + 16 * g + fk + 4 * q;
+        P[c * 16 + fr] = c < n ? P[c * 16 + fr] - (sum[q] + red[(g * 4 + q) * 64 + lane]) : 0.0;
+      }
+    }
+    __syncthreads();
+    // X_j = op(invD_j) R_j, reduction over kk split between the two halves
+    double4_t t0 = (double4_t){0.0, 0.0, 0.0, 0.0}, t1 = t0;
+    const double* __restrict__ Dj = invD + (size_t)jb * 4096 + (tr ? (16 * g + fr) * 64 : 16 * g + fr);
+    const int dk = tr ? 1 : 64;
+#pragma unroll
+    for (int kk = 32 * h; kk < 32 * h + 32; kk += 8) {
+      const double a0 = Dj[(kk + fk) * dk], a1 = Dj[(kk + 4 + fk) * dk];
+      const double b0 = P[(c0 + kk + fk) * 16 + fr], b1 = P[(c0 + kk + 4 + fk) * 16 + fr];
+      t0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, t0, 0, 0, 0);
+      t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, t1, 0, 0, 0);
+    }
+    double4_t t = t0 + t1;
+    if (h == 1) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) red[(g * 4 + q) * 64 + lane] = t[q];
+    }
+    __syncthreads();  // every wave has read R_j
+    if (h == 0) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int c = c0 + 16 * g + fk + 4 * q;
+        P[c * 16 + fr] = c < n ? t[q] + red[(g * 4 + q) * 64 + lane] : 0.0;
+      }
+    }
+    __syncthreads();
+  }
+  for (int idx = tid; idx < n * 16; idx += kTrsmThreads) {
+    const int i = idx >> 4, jj = idx & 15;
+    if (j0 + jj < nrhs) Bp[(size_t)(j0 + jj) * ldb + i] = P[idx];
+  }
+}
+
 // ================================================================ launchers
 static int g_gemm_tile_policy = -1;  // -1 unset, 0 auto, 64, 128
 static int g_gemm_variant = -1;      // big-tile kernel shape (PARSEC_GEMM_VARIANT)
@@ -1363,6 +1490,69 @@ void launch_trsm_batch(const TrsmDesc* descs, int n, hipStream_t stream, double*
     inv[i] = blk;
   }
   launch_trsm_inv(descs, inv.data(), n, stream);
+}
+
+void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(dtrtri_diag_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, L, ldl, n, invD);
+}
+
+size_t trsm_left_workspace_bytes(const TrsmLeftDesc* descs, int n) {
+  size_t bytes = 0;
+  std::vector<const double*> seen;
+  for (int i = 0; i < n; ++i) {
+    if (descs[i].invD || descs[i].n <= 0) continue;
+    if (std::find(seen.begin(), seen.end(), descs[i].L) != seen.end()) continue;
+    seen.push_back(descs[i].L);
+    bytes += (size_t)((descs[i].n + 63) / 64) * 4096 * sizeof(double);
+  }
+  return bytes;
+}
+
+// Left-side solves, one workgroup per 16 columns of every B. Diagonal-block
+// inverses come from the descriptor or are computed once per distinct L into ws.
+void launch_trsm_left_batch(const TrsmLeftDesc* descs, int n, hipStream_t stream, double* ws) {
+  if (n <= 0) return;
+  static bool attr = false;
+  if (!attr) {
+    (void)hipFuncSetAttribute((const void*)dtrsm_left_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    attr = true;
+  }
+  std::vector<std::pair<const double*, const double*>> seen;  // L -> inverse blocks
+  std::vector<const double*> inv(n, nullptr);
+  size_t off = 0;
+  for (int i = 0; i < n; ++i) {
+    if (descs[i].n <= 0 || descs[i].nrhs <= 0) continue;
+    if (descs[i].invD) { inv[i] = descs[i].invD; continue; }
+    auto it = std::find_if(seen.begin(), seen.end(), [&](const auto& e) { return e.first == descs[i].L; });
+    if (it != seen.end()) { inv[i] = it->second; continue; }
+    int nblk = (descs[i].n + 63) / 64;
+    double* blk = ws + off;
+    off += (size_t)nblk * 4096;
+    hipLaunchKernelGGL(dtrtri_diag_kernel, dim3(nblk), dim3(kDiagThreads), 0, stream, descs[i].L, descs[i].ldl, descs[i].n, blk);
+    seen.emplace_back(descs[i].L, blk);
+    inv[i] = blk;
+  }
+  for (int s0 = 0; s0 < n; s0 += kMaxTrsmLeftBatch) {
+    const int cnt = std::min(kMaxTrsmLeftBatch, n - s0);
+    TrsmLeftArgs a;
+    a.count = cnt;
+    a.prio = t_launch_prio;
+    int total = 0, maxn = 0;
+    for (int i = 0; i < cnt; ++i) {
+      a.d[i] = descs[s0 + i];
+      a.d[i].invD = inv[s0 + i];
+      a.block_start[i] = total;
+      if (a.d[i].n <= 0 || a.d[i].nrhs <= 0) continue;
+      total += (a.d[i].nrhs + 15) / 16;
+      maxn = std::max(maxn, a.d[i].n);
+    }
+    a.block_start[cnt] = total;
+    if (total == 0) continue;
+    if (maxn > kTrsmMaxCols) fatal("dtrsm left tile kernel: n=%d exceeds the LDS-resident strip limit %d", maxn, kTrsmMaxCols);
+    const size_t lds = ((size_t)((maxn + 63) / 64) * 64 * 16 + 1024) * sizeof(double);
+    hipLaunchKernelGGL(dtrsm_left_kernel, dim3(total), dim3(kTrsmThreads), lds, stream, a);
+  }
 }
 
 __global__ void set_identity_kernel(double* W, int n, int ldw) {
@@ -2858,6 +3048,7 @@ size_t kernel_batch_workspace_bytes(const KernelBatch& b) {
   if (!b.trsm_w.empty()) w = std::max(w, kern::trsm_w_workspace_bytes(b.trsm_w.data(), (int)b.trsm_w.size()));
   if (!b.qr_panel.empty()) w = std::max(w, kern::qr_panel_workspace_bytes(b.qr_panel.data(), (int)b.qr_panel.size()));
   w = std::max(w, kern::trsm_workspace_bytes(b.trsm.data(), (int)b.trsm.size()));
+  w = std::max(w, kern::trsm_left_workspace_bytes(b.trsm_left.data(), (int)b.trsm_left.size()));
   return std::max(w, kern::qr_apply_workspace_bytes(b.qr_apply.data(), (int)b.qr_apply.size()));
 }
 
@@ -2888,6 +3079,7 @@ void launch_kernel_batch(KernelBatch& b, hipStream_t stream, int device_ordinal,
   if (!b.qr_panel.empty()) kern::launch_qr_panel_blocked(b.qr_panel.data(), (int)b.qr_panel.size(), stream, static_cast<double*>(ws));
   if (!b.trsm.empty()) kern::launch_trsm_batch(b.trsm.data(), (int)b.trsm.size(), stream, static_cast<double*>(ws));
   if (!b.trsm_w.empty()) kern::launch_trsm_w_batch(b.trsm_w.data(), (int)b.trsm_w.size(), stream, static_cast<double*>(ws));
+  if (!b.trsm_left.empty()) kern::launch_trsm_left_batch(b.trsm_left.data(), (int)b.trsm_left.size(), stream, static_cast<double*>(ws));
   if (!b.qr_apply.empty()) kern::launch_qr_apply(b.qr_apply.data(), (int)b.qr_apply.size(), stream, static_cast<double*>(ws));
   if (!b.gemm.empty()) kern::launch_gemm_batch(b.gemm.data(), (int)b.gemm.size(), stream);
   if (!b.stencil.empty()) kern::launch_stencil7_batch(b.stencil.data(), (int)b.stencil.size(), stream);
@@ -3057,6 +3249,13 @@ int parsec_amd_dgemm(char transa, char transb, int m, int n, int k, double alpha
 int parsec_amd_dtrsm_batch(const parsec::TrsmDesc* descs, int n, void* stream) {
   void* ws = test_ws(parsec::kern::trsm_workspace_bytes(descs, n) + 64);
   parsec::kern::launch_trsm_batch(descs, n, (hipStream_t)stream, static_cast<double*>(ws));
+  return (int)hipGetLastError();
+}
+// B := alpha op(L)^-1 B for a batch; descriptors without invD get their
+// diagonal-block inverses computed into cached scratch
+int parsec_amd_dtrsm_left_batch(const parsec::TrsmLeftDesc* descs, int n, void* stream) {
+  void* ws = test_ws(parsec::kern::trsm_left_workspace_bytes(descs, n) + 64);
+  parsec::kern::launch_trsm_left_batch(descs, n, (hipStream_t)stream, static_cast<double*>(ws));
   return (int)hipGetLastError();
 }
 int parsec_amd_dpotrf_tile(double* A, int n, int lda, int* info, void* stream) {

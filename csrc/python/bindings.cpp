@@ -30,6 +30,7 @@ extern "C" int parsec_amd_gemm_mainloop(int mode);
 extern "C" int parsec_amd_potrf_steps(int on);
 extern "C" int parsec_amd_potrf_stamps(long long* out);
 extern "C" int parsec_amd_dtrsm_batch(const TrsmDesc* descs, int n, void* stream);
+extern "C" int parsec_amd_dtrsm_left_batch(const TrsmLeftDesc* descs, int n, void* stream);
 extern "C" int parsec_amd_dpotrf_tile(double* A, int n, int lda, int* info, void* stream);
 extern "C" int parsec_amd_trsm_w_batch(const parsec::TrsmGemmDesc* d, int n, void* stream);
 extern "C" int parsec_amd_dpotrf_tile_w(double* A, int n, int lda, int* info, double* W, int ldw, void* stream, int pack);
@@ -139,6 +140,13 @@ PYBIND11_MODULE(_C, m) {
   m.attr("MATRIX_COMPLEX_DOUBLE") = (int)MATRIX_COMPLEX_DOUBLE;
   m.attr("MATRIX_FULL") = (int)MATRIX_FULL;
   m.attr("MATRIX_LOWER") = (int)MATRIX_LOWER;
+  m.attr("MATRIX_NOTRANS") = (int)MATRIX_NOTRANS;
+  m.attr("MATRIX_TRANS") = (int)MATRIX_TRANS;
+  m.attr("MATRIX_CONJTRANS") = (int)MATRIX_CONJTRANS;
+  m.attr("MATRIX_NONUNIT") = (int)MATRIX_NONUNIT;
+  m.attr("MATRIX_UNIT") = (int)MATRIX_UNIT;
+  m.attr("MATRIX_LEFT") = (int)MATRIX_LEFT;
+  m.attr("MATRIX_RIGHT") = (int)MATRIX_RIGHT;
   m.attr("MATRIX_UPPER") = (int)MATRIX_UPPER;
 
   // --------------------------------------------------------------- params
@@ -503,6 +511,26 @@ PYBIND11_MODULE(_C, m) {
         tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
         return py::make_tuple(py::cast(tp, py::return_value_policy::take_ownership), (uintptr_t)info);
       }, "tiled Cholesky (lower) from the ptgpp-compiled algos/jdf/dpotrf_L.jdf; returns (taskpool, info address)");
+  m.def("dtrsm_new", [](int side, int uplo, int trans, int diag, double alpha, TiledMatrix* A, TiledMatrix* B) {
+        return algos::dtrsm_new(side, uplo, trans, diag, alpha, A, B);
+      }, py::arg("side"), py::arg("uplo"), py::arg("trans"), py::arg("diag"), py::arg("alpha"), py::arg("A"), py::arg("B"), py::return_value_policy::take_ownership,
+      "tiled triangular solve B := alpha op(A)^-1 B (MATRIX_LEFT, MATRIX_LOWER, MATRIX_NOTRANS / MATRIX_TRANS, MATRIX_NONUNIT) from the ptgpp-compiled "
+      "dtrsm_LL.jdf; B.mb must equal A.nb; None for anything else");
+  // composed taskpools: release with taskpool_free (it frees the parts too)
+  m.def("dpotrs_new", [](int uplo, TiledMatrix* A, TiledMatrix* B) { return algos::dpotrs_new(uplo, A, B); }, py::arg("uplo"), py::arg("A"), py::arg("B"),
+        py::return_value_policy::reference, "solve A X = B with the Cholesky factor in A (lower): B := L^-T L^-1 B; None on invalid arguments");
+  m.def("dposv_new", [](int uplo, TiledMatrix* A, TiledMatrix* B) -> py::object {
+        auto* info = new int(0);
+        Taskpool* tp = algos::dposv_new(uplo, A, B, info);
+        if (!tp) {
+          delete info;
+          return py::none();
+        }
+        auto prev = tp->destructor_hook;
+        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
+        return py::make_tuple(py::cast(tp, py::return_value_policy::reference), (uintptr_t)info);
+      }, py::arg("uplo"), py::arg("A"), py::arg("B"),
+      "Cholesky factorization then solve (lower, one rank); returns (taskpool, info address) or None. When info != 0 the solve does not run and B is untouched");
   m.def("dgeqrf_jdf_new", [](TiledMatrix* A, TiledMatrix* T) { return algos::dgeqrf_jdf_new(A, T); }, py::arg("A"), py::arg("T"),
         py::return_value_policy::take_ownership, "Tiled QR from the ptgpp-compiled dgeqrf.jdf (GEQRT / TSQRT / UNMQR / TSMQR)");
   m.def("dgeqrf_new", [](TiledMatrix* A, TiledMatrix* T, int ib) { return algos::dgeqrf_new(A, T, ib); }, py::arg("A"), py::arg("T"), py::arg("ib") = 0,
@@ -719,6 +747,19 @@ PYBIND11_MODULE(_C, m) {
     TrsmDesc t;
     t.L = (const double*)L; t.B = (double*)B; t.m = mm; t.n = nn; t.ldl = ldl; t.ldb = ldb; t.trans = 1;
     return parsec_amd_dtrsm_batch(&t, 1, (void*)stream);
+  });
+  m.def("kernel_dtrsm_left", [](uintptr_t L, uintptr_t B, int n, int nrhs, int ldl, int ldb, double alpha, int trans, uintptr_t stream) {
+    TrsmLeftDesc t{(const double*)L, (double*)B, n, nrhs, ldl, ldb, alpha, (uint8_t)(trans ? 1 : 0), nullptr};
+    return parsec_amd_dtrsm_left_batch(&t, 1, (void*)stream);
+  }, py::arg("L"), py::arg("B"), py::arg("n"), py::arg("nrhs"), py::arg("ldl"), py::arg("ldb"), py::arg("alpha") = 1.0, py::arg("trans") = 0, py::arg("stream") = 0,
+     "B := alpha op(L)^-1 B on the GPU: L n x n lower (column-major, only the lower triangle is read), B n x nrhs; trans 1 solves with L^T");
+  // grouped launch: tuples (L, B, n, nrhs, ldl, ldb, alpha, trans)
+  m.def("kernel_dtrsm_left_batch", [](const std::vector<std::tuple<uintptr_t, uintptr_t, int, int, int, int, double, int>>& ds, uintptr_t stream) {
+    std::vector<TrsmLeftDesc> v;
+    for (const auto& d : ds)
+      v.push_back(TrsmLeftDesc{(const double*)std::get<0>(d), (double*)std::get<1>(d), std::get<2>(d), std::get<3>(d), std::get<4>(d), std::get<5>(d),
+                               std::get<6>(d), (uint8_t)(std::get<7>(d) ? 1 : 0), nullptr});
+    return parsec_amd_dtrsm_left_batch(v.data(), (int)v.size(), (void*)stream);
   });
   m.def("kernel_qr_panel", [](uintptr_t A1, int lda1, uintptr_t A2, int lda2, uintptr_t T, int ldt, uintptr_t V, int m1, int m2, int n, uintptr_t stream) {
     QrPanelDesc q{};

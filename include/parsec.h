@@ -489,6 +489,10 @@ void parsec_data_free(void* ptr);
 typedef enum { PARSEC_MATRIX_BYTE = 0, PARSEC_MATRIX_INTEGER, PARSEC_MATRIX_FLOAT, PARSEC_MATRIX_DOUBLE, PARSEC_MATRIX_COMPLEX_FLOAT, PARSEC_MATRIX_COMPLEX_DOUBLE } parsec_matrix_type_t;
 typedef enum { PARSEC_MATRIX_LAPACK = 0, PARSEC_MATRIX_TILE = 1 } parsec_matrix_storage_t;
 typedef enum { PARSEC_MATRIX_FULL = 0, PARSEC_MATRIX_LOWER = 1, PARSEC_MATRIX_UPPER = 2 } parsec_matrix_uplo_t;
+/* BLAS-style selectors of the linear-algebra taskpools (DPLASMA / PLASMA values) */
+typedef enum { PARSEC_MATRIX_NOTRANS = 111, PARSEC_MATRIX_TRANS = 112, PARSEC_MATRIX_CONJTRANS = 113 } parsec_matrix_trans_t;
+typedef enum { PARSEC_MATRIX_NONUNIT = 131, PARSEC_MATRIX_UNIT = 132 } parsec_matrix_diag_t;
+typedef enum { PARSEC_MATRIX_LEFT = 141, PARSEC_MATRIX_RIGHT = 142 } parsec_matrix_side_t;
 
 typedef struct parsec_tiled_matrix_s {
   parsec_data_collection_t super;
@@ -657,6 +661,21 @@ parsec_taskpool_t* parsec_apply_New(parsec_matrix_uplo_t uplo, parsec_tiled_matr
  * dplasma_dpotrf_New role): HIP bodies on GPUs, CPU bodies otherwise. *info
  * holds the LAPACK info once the taskpool completed (0: success). */
 parsec_taskpool_t* parsec_dpotrf_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, int* info);
+/* Tiled triangular solve B := alpha op(A)^-1 B of double matrices (DPLASMA's
+ * dplasma_dtrsm_New role, the ptgpp-compiled dtrsm_LL.jdf): PARSEC_MATRIX_LEFT,
+ * PARSEC_MATRIX_LOWER, PARSEC_MATRIX_NOTRANS or PARSEC_MATRIX_TRANS,
+ * PARSEC_MATRIX_NONUNIT. A is N x N with square tiles, B is N x NRHS with
+ * B->mb == A->nb; the two may be distributed on different process grids. NULL
+ * (after a warning) for any other combination or shape. */
+parsec_taskpool_t* parsec_dtrsm_New(parsec_matrix_side_t side, parsec_matrix_uplo_t uplo, parsec_matrix_trans_t trans, parsec_matrix_diag_t diag,
+                                    double alpha, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B);
+/* Solve A X = B with the factor parsec_dpotrf_New left in A (PARSEC_MATRIX_LOWER
+ * only): B := L^-T L^-1 B, two dtrsm sweeps composed. NULL on invalid arguments. */
+parsec_taskpool_t* parsec_dpotrs_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B);
+/* parsec_dpotrf_New then parsec_dpotrs_New in one taskpool. When the
+ * factorization fails (*info != 0) the solve does not run and B is untouched.
+ * One rank only: NULL on more (factor, check info, then parsec_dpotrs_New). */
+parsec_taskpool_t* parsec_dposv_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info);
 int parsec_apply(parsec_context_t* parsec, parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_unary_op_t operation, void* op_args);
 /* op(es, src_tile, dest_tile, op_data, m, n) for every tile of dest */
 parsec_taskpool_t* parsec_map_operator_New(const parsec_tiled_matrix_t* src, parsec_tiled_matrix_t* dest, parsec_operator_t op, void* op_data);
