@@ -11,6 +11,13 @@
            A factored once outside the timed region, every timed step restores B
            and solves, GFLOP/s with 2 N^2 NRHS; the same process then times
            torch.cholesky_solve on the dense factor (what a user does without it)
+  gels     least squares with the tile QR factor, M >= N: DGEQRS (dormqr.jdf then
+           dtrsm_LU.jdf on a factor computed once outside the timed region) and
+           DGELS (DGEQRF + DGEQRS in one taskpool), B (and for DGELS A, T)
+           restored every timed step, GFLOP/s with 4 M N NRHS - N^2 NRHS (plus
+           2 M N^2 - 2/3 N^3 for DGELS); the same process then times a torch
+           yardstick on the dense data: torch.linalg.lstsq if it runs on the
+           device, otherwise torch.linalg.qr + solve_triangular
 
 Multi-GPU: launch like bench.py (torch.distributed.run, one rank per GPU).
 
@@ -18,6 +25,7 @@ Multi-GPU: launch like bench.py (torch.distributed.run, one rank per GPU).
     python benchmarks/bench_workloads.py stencil --n 512 --b 128 --iters 20
     python benchmarks/bench_workloads.py dtd_gemm --n 2048
     python benchmarks/bench_workloads.py potrs --n 16384 --nb 512 --nrhs 16384
+    python benchmarks/bench_workloads.py gels --m 32768 --n 8192 --nb 512 --nrhs 512
 """
 import argparse
 import json
@@ -340,14 +348,142 @@ def bench_potrs(args):
     return out, 0
 
 
+def bench_gels(args):
+    import torch
+
+    import parsec_amd as pa
+
+    world, rank, local = _dist()
+    if world > 1:
+        raise RuntimeError("gels: one GPU (the yardstick is a single-device torch solve)")
+    if not torch.cuda.is_available():
+        raise RuntimeError("gels: no GPU")
+    M, N, nb, NRHS = args.m, args.n, args.nb, args.nrhs
+    if M < N:
+        raise RuntimeError("gels: M >= N")
+    nbr = args.nbr or min(nb, NRHS)
+    dev = torch.device("cuda", 0)
+    ctx = pa.init(args.cores)
+    gpu = pa.first_gpu_device_index()
+    if gpu < 0:
+        raise RuntimeError("no GPU device registered in the runtime")
+    MT, NT, NTB = -(-M // nb), -(-N // nb), -(-NRHS // nbr)
+
+    def run(tp):
+        ctx.add_taskpool(tp)
+        ctx.start()
+        ctx.wait()
+
+    def tiled(dense, rows, cols, mt, nt, mb, cb):  # the store image [n][m][col][row] of a dense matrix
+        pad = torch.zeros((mt * mb, nt * cb), dtype=torch.float64, device=dev)
+        pad[:rows, :cols] = dense
+        return pad.reshape(mt, mb, nt, cb).permute(2, 0, 3, 1).contiguous()
+
+    def dense_of(store, rows, cols, mb, cb):  # a dense COPY of a tiled store
+        return store.permute(1, 3, 0, 2).reshape(store.shape[1] * mb, store.shape[0] * cb)[:rows, :cols].contiguous()
+
+    gen = torch.Generator(device=dev).manual_seed(12345)
+    S = torch.rand((M, N), dtype=torch.float64, device=dev, generator=gen) - 0.5
+    B0 = torch.rand((M, NRHS), dtype=torch.float64, device=dev, generator=gen) - 0.5
+    backupA = tiled(S, M, N, MT, NT, nb, nb)
+    backupB = tiled(B0, M, NRHS, MT, NTB, nb, nbr)
+    sa = backupA.clone()
+    st = torch.zeros_like(sa)
+    sb = backupB.clone()
+    A = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nb, M, N, device=gpu, ptr=sa.data_ptr())
+    T = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nb, M, N, device=gpu, ptr=st.data_ptr())
+    B = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nbr, M, NRHS, device=gpu, ptr=sb.data_ptr())
+    torch.cuda.synchronize()
+
+    def step_gels():
+        sa.copy_(backupA)
+        st.zero_()
+        sb.copy_(backupB)
+        torch.cuda.synchronize()
+        tp = pa.dgels_new(A, T, B)
+        run(tp)
+        pa.taskpool_free(tp)
+
+    def step_geqrs():
+        sb.copy_(backupB)
+        torch.cuda.synchronize()
+        tp = pa.dgeqrs_new(A, T, B)
+        run(tp)
+        pa.taskpool_free(tp)
+
+    def timed(step):
+        for _ in range(args.warmup):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps
+
+    def normal_residual():
+        X = dense_of(sb, M, NRHS, nb, nbr)[:N]
+        nS, nB = torch.linalg.norm(S), torch.linalg.norm(B0)
+        return X, float(torch.linalg.norm(S.t() @ (S @ X - B0)) / (nS * nS * torch.linalg.norm(X) + nS * nB))
+
+    # DGELS first: it leaves the factor in A and T for the DGEQRS steps
+    dt_gels = timed(step_gels)
+    X, resid_gels = normal_residual()
+    dt_geqrs = timed(step_geqrs)
+    X, resid = normal_residual()
+    if not (resid < 1e-13 and resid_gels < 1e-13):
+        raise RuntimeError(f"normal-equations residual too large: dgeqrs {resid:.3e}, dgels {resid_gels:.3e}")
+    flops_solve = 4.0 * M * N * NRHS - 2.0 * N * N * NRHS + 1.0 * N * N * NRHS
+    flops_qr = 2.0 * M * N * N - 2.0 / 3.0 * N ** 3
+    # yardstick on the dense data (factor and solve, what DGELS does): lstsq if
+    # the device runs it, otherwise QR + triangular solve
+    del sa, st, backupA
+
+    def y_lstsq():
+        return torch.linalg.lstsq(S, B0).solution
+
+    def y_qr():
+        Q, R = torch.linalg.qr(S)
+        return torch.linalg.solve_triangular(R, Q.t() @ B0, upper=True)
+
+    yard, yname = y_lstsq, "torch.linalg.lstsq"
+    try:
+        Y = yard()
+        torch.cuda.synchronize()
+        if not bool(torch.isfinite(Y).all()):
+            raise RuntimeError("non-finite")
+    except Exception as e:  # not available on this device / build
+        yard, yname = y_qr, f"torch.linalg.qr + solve_triangular (lstsq did not run: {type(e).__name__})"
+    for _ in range(max(1, args.warmup)):
+        Y = yard()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        Y = yard()
+    torch.cuda.synchronize()
+    dty = (time.perf_counter() - t0) / args.steps
+    diff = float(torch.linalg.norm(X - Y) / torch.linalg.norm(Y))
+    ctx.fini()
+    out = {"metric": "GFLOP/s DGEQRS (dormqr.jdf + dtrsm_LU.jdf, HBM-resident tiles, B restored every step)", "value": round(flops_solve / dt_geqrs / 1e9, 1),
+           "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt_geqrs * 1e3, 3), "higher_is_better": True,
+           "dtype": "fp64", "normal_equations_residual": resid,
+           "dgels_gflops": round((flops_qr + flops_solve) / dt_gels / 1e9, 1), "dgels_ms": round(dt_gels * 1e3, 3), "dgels_normal_equations_residual": resid_gels,
+           "yardstick": yname + " on the dense data (factor and solve), same process",
+           "yardstick_gflops": round((flops_qr + flops_solve) / dty / 1e9, 1), "yardstick_ms": round(dty * 1e3, 3), "dgels_ratio_to_yardstick": round(dty / dt_gels, 3),
+           "rel_diff_to_yardstick": diff,
+           "config": {"model": "DGELS", "M": M, "N": N, "nb": nb, "NRHS": NRHS, "nbr": nbr, "cores": args.cores}}
+    return out, 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm", "potrs"])
+    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm", "potrs", "gels"])
     ap.add_argument("--n", "--size", dest="n", type=int, default=None, help="matrix order (use --size under torchrun)")
+    ap.add_argument("--m", type=int, default=None, help="gels: rows of A (default: n)")
     ap.add_argument("--nb", type=int, default=512)
     ap.add_argument("--ib", type=int, default=32, help="qr: accepted for the reference's command line; both taskpools factor 32-column sub-panels (qr_sub2c) and apply one nb x nb block reflector per tile")
-    ap.add_argument("--nrhs", type=int, default=None, help="potrs: right-hand sides (default: n)")
-    ap.add_argument("--nbr", type=int, default=0, help="potrs: tile width of B (default: min(nb, nrhs))")
+    ap.add_argument("--nrhs", type=int, default=None, help="potrs / gels: right-hand sides (default: n)")
+    ap.add_argument("--nbr", type=int, default=0, help="potrs / gels: tile width of B (default: min(nb, nrhs))")
     ap.add_argument("--b", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=2)
@@ -362,10 +498,12 @@ def main():
                     help="qr: rows per TS domain of the hierarchical tree (0: one flat TS chain per process row, TT binary tree across process rows; 1 GPU measured fastest flat: profiles/r3_qr_tree_ab.jsonl)")
     args = ap.parse_args()
     if args.n is None:
-        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048, "potrs": 16384}[args.workload]
+        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048, "potrs": 16384, "gels": 16384}[args.workload]
     if args.nrhs is None:
         args.nrhs = args.n
-    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm, "potrs": bench_potrs}[args.workload]
+    if args.m is None:
+        args.m = args.n
+    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm, "potrs": bench_potrs, "gels": bench_gels}[args.workload]
     out, rank = fn(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -109,7 +109,8 @@ void cpu_tsqrt(int m2, int n, double* A1, int lda1, double* A2, int lda2, double
 }
 
 // W (n x nc) = op(V)^T ... helpers on column-major arrays
-static void cpu_apply(const double* V, int ldv, int vrows, bool unit_lower, const double* T, int ldt, double* A1, int lda1, double* A2, int lda2, int n, int nc) {
+static void cpu_apply(const double* V, int ldv, int vrows, bool unit_lower, const double* T, int ldt, double* A1, int lda1, double* A2, int lda2, int n, int nc,
+                      bool notrans = false) {
   // W = (A1 ? A1 : 0) + V^T A2
   std::vector<double> W((size_t)n * nc, 0.0), W2((size_t)n * nc, 0.0);
   auto v = [&](int r, int c) -> double {
@@ -122,11 +123,14 @@ static void cpu_apply(const double* V, int ldv, int vrows, bool unit_lower, cons
       for (int r = 0; r < vrows; ++r) w += v(r, i) * A2[r + (size_t)c * lda2];
       W[i + (size_t)c * n] = w;
     }
-  // W2 = T^T W (T upper)
+  // W2 = T^T W (Q^T), or T W (Q: notrans); T upper
   for (int c = 0; c < nc; ++c)
     for (int i = 0; i < n; ++i) {
       double w = 0.0;
-      for (int l = 0; l <= i; ++l) w += T[l + (size_t)i * ldt] * W[l + (size_t)c * n];
+      if (notrans)
+        for (int l = i; l < n; ++l) w += T[i + (size_t)l * ldt] * W[l + (size_t)c * n];
+      else
+        for (int l = 0; l <= i; ++l) w += T[l + (size_t)i * ldt] * W[l + (size_t)c * n];
       W2[i + (size_t)c * n] = w;
     }
   if (A1)
@@ -142,6 +146,12 @@ static void cpu_apply(const double* V, int ldv, int vrows, bool unit_lower, cons
 
 void cpu_qr_apply(const double* V, int ldv, int vrows, bool unit_lower, const double* T, int ldt, double* A1, int lda1, double* A2, int lda2, int n, int nc) {
   cpu_apply(V, ldv, vrows, unit_lower, T, ldt, A1, lda1, A2, lda2, n, nc);
+}
+
+// The same with the op: notrans applies Q = I - V T V^T instead of Q^T.
+void cpu_qr_apply_op(const double* V, int ldv, int vrows, bool unit_lower, const double* T, int ldt, double* A1, int lda1, double* A2, int lda2, int n, int nc,
+                     bool notrans) {
+  cpu_apply(V, ldv, vrows, unit_lower, T, ldt, A1, lda1, A2, lda2, n, nc, notrans);
 }
 
 // ---------------------------------------------------------------- taskpool

@@ -40,6 +40,21 @@ ptg::PtgTaskpool* dgeqrf_new(TiledMatrix* A, TiledMatrix* T, int ib);
 // The same factorization from the JDF source algos/jdf/dgeqrf.jdf, compiled by
 // parsec-ptgpp at build time (the benchmark's taskpool).
 ptg::PtgTaskpool* dgeqrf_jdf_new(TiledMatrix* A, TiledMatrix* T);
+// B := op(Q) B with the Q that dgeqrf_jdf_new / dgeqrf_new (the flat-tree
+// taskpools; NOT dgeqrf_hqr_new) left in A and T, from the JDF source
+// algos/jdf/dormqr.jdf: side Left, trans Trans or NoTrans. A is M x N with square
+// tiles, T is tiled like A, B is M x NRHS with B->mb == A->mb and any tile width;
+// A / T and B may be distributed differently. Any other request returns nullptr
+// after a warning.
+ptg::PtgTaskpool* dormqr_new(int side, int trans, TiledMatrix* A, TiledMatrix* T, TiledMatrix* B);
+// The minimiser of ||A X - B||_F (M >= N) from that factor: Q^T B composed with
+// the solve with R (algos/jdf/dtrsm_LU.jdf). On return rows 0..N-1 of B hold X
+// and rows N..M-1 the residual components, whose column norms are the residual
+// norms (LAPACK DGELS convention). A singular R yields inf / nan as in LAPACK.
+// Freeing the returned taskpool (taskpool_free) frees its parts.
+Taskpool* dgeqrs_new(TiledMatrix* A, TiledMatrix* T, TiledMatrix* B);
+// dgeqrf_jdf_new composed with dgeqrs_new: A and T are overwritten with the factor.
+Taskpool* dgels_new(TiledMatrix* A, TiledMatrix* T, TiledMatrix* B);
 // Hierarchical QR (dgeqrf_hqr.cpp): TS domains of `domain` rows per process row
 // (<= 0: all of them, i.e. flat inside a process row),
 // TT binary trees over domain heads and across the p_rows process rows (<= 0:

@@ -1129,6 +1129,16 @@ parsec_taskpool_t* parsec_dpotrs_New(parsec_matrix_uplo_t uplo, parsec_tiled_mat
 parsec_taskpool_t* parsec_dposv_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info) {
   return algos::dposv_new((int)uplo, tm_of(A), tm_of(B), info);
 }
+parsec_taskpool_t* parsec_dormqr_New(parsec_matrix_side_t side, parsec_matrix_trans_t trans, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* T,
+                                     parsec_tiled_matrix_t* B) {
+  return algos::dormqr_new((int)side, (int)trans, tm_of(A), tm_of(T), tm_of(B));
+}
+parsec_taskpool_t* parsec_dgeqrs_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* T, parsec_tiled_matrix_t* B) {
+  return algos::dgeqrs_new(tm_of(A), tm_of(T), tm_of(B));
+}
+parsec_taskpool_t* parsec_dgels_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* T, parsec_tiled_matrix_t* B) {
+  return algos::dgels_new(tm_of(A), tm_of(T), tm_of(B));
+}
 int parsec_apply(parsec_context_t* parsec, parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_unary_op_t operation, void* op_args) {
   parsec_taskpool_t* tp = parsec_apply_New(uplo, A, operation, op_args);
   parsec_context_add_taskpool(parsec, tp);

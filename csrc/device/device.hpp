@@ -127,16 +127,20 @@ struct TrsmDesc {  // B := B * op(L)^-1 ; right side, lower, (trans), non-unit
   const double* invD = nullptr;  // optional: inverses of L's 64x64 diagonal blocks (from POTRF)
   const double* gate_slot = nullptr;  // gate: max|L|, max|W| of the panel (workspace)
 };
-// B := alpha * op(L)^-1 B ; left side, lower, non-unit. L is n x n column-major
-// (only its lower triangle is used), B is n x nrhs.
+// B := alpha * op(L)^-1 B ; left side, non-unit, L lower (default) or upper. L
+// is n x n column-major and only the named triangle is read (the other one may
+// hold anything: the V of a QR diagonal tile), B is n x nrhs.
 struct TrsmLeftDesc {
   const double* L;
   double* B;
   int n, nrhs;
   int ldl, ldb;
   double alpha;
-  uint8_t trans;  // 0: L^-1 B (forward sweep), 1: L^-T B (backward sweep)
-  const double* invD;  // optional: inverses of L's 64x64 diagonal blocks, contiguous 4096-double blocks (dtrtri_diag_kernel)
+  uint8_t trans;  // 0: L^-1 B (lower: forward sweep, upper: backward), 1: L^-T B (the other direction)
+  uint8_t upper = 0;  // 1: L is upper triangular (the R of a QR factor)
+  // optional: inverses of L's 64x64 diagonal blocks (of the same triangle),
+  // contiguous 4096-double blocks (dtrtri_diag_kernel / dtrtri_diag_upper_kernel)
+  const double* invD = nullptr;
 };
 static_assert(sizeof(GemmDesc) == 96, "GemmDesc grew: the grouped-GEMM kernel argument block is sized for 40 of them");
 
@@ -178,6 +182,13 @@ namespace kern {
 // Inverses of the 64 x 64 diagonal blocks of L (n x n lower, ld ldl) into invD:
 // block b at invD + b * 4096, column-major, padded with the identity
 void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream);
+// the same for U (n x n upper): the blocks of invD are upper triangular; U's
+// strict lower triangle is never read
+void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipStream_t stream);
+// Vout (rows x min(rows, cols), ld rows) := the unit-lower V stored below the
+// diagonal of a factored QR diagonal tile A (ld lda): ones on the diagonal,
+// zeros above (the layout of QrPanelDesc::Vcopy)
+void launch_qr_extract_v(const double* A, int lda, int rows, int cols, double* Vout, hipStream_t stream);
 // device_hip_cu_yield as the kernels see it (QR sub-panel kernels claim their CUs when > 0)
 void set_cu_yield_mode(int m);
 int cu_yield_mode();
@@ -214,9 +225,9 @@ struct QrPanelDesc {
   int ldtri;
 };
 
-// Apply Q^T of a QR panel: UNMQR (A1 == nullptr: C = A2 := Q^T C with C and the
-// unit-lower V both m2 rows, n reflectors) or TSMQR ([A1; A2] := Q^T [A1; A2]
-// with V = [I; V2], V2 m2 x n, A1 n x ncols).
+// Apply Q^T (or Q: notrans) of a QR panel: UNMQR (A1 == nullptr: C = A2 := Q^T C
+// with C and the unit-lower V both m2 rows, n reflectors) or TSMQR ([A1; A2] :=
+// Q^T [A1; A2] with V = [I; V2], V2 m2 x n, A1 n x ncols).
 struct QrApplyDesc {
   const double* V;
   int ldv;
@@ -227,6 +238,7 @@ struct QrApplyDesc {
   double* A2;
   int lda2;
   int m2, n, ncols;
+  uint8_t notrans = 0;  // 1: apply Q = I - V T V^T instead of Q^T = I - V T^T V^T
 };
 
 // One block update of the DTD 3D 7-point stencil (stencil_kernels.hip).

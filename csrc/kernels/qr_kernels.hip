@@ -1497,6 +1497,20 @@ size_t qr_apply_workspace_bytes(const QrApplyDesc* descs, int n) {
   return b;
 }
 
+// Clean unit-lower V of a factored diagonal tile: Vout (rows x kr, ld rows) takes
+// the part of A below the diagonal, ones on it and zeros above (R stays in A).
+__global__ __launch_bounds__(256) void qr_extract_v_kernel(const double* __restrict__ A, int lda, int rows, double* __restrict__ Vout) {
+  const int c = blockIdx.y;  // < kr
+  const int r = blockIdx.x * 256 + threadIdx.x;
+  if (r < rows) Vout[(size_t)c * rows + r] = r > c ? A[(size_t)c * lda + r] : (r == c ? 1.0 : 0.0);
+}
+
+void launch_qr_extract_v(const double* A, int lda, int rows, int cols, double* Vout, hipStream_t stream) {
+  const int kr = std::min(rows, cols);
+  if (kr <= 0) return;
+  hipLaunchKernelGGL(qr_extract_v_kernel, dim3((rows + 255) / 256, kr), dim3(256), 0, stream, A, lda, rows, Vout);
+}
+
 // Q^T application over all descriptors in three grouped MFMA launches
 // (Q^T = I - V T^T V^T, T upper with zeros below):
 //   1. W  = V^T C2 (+ A1)                 (TSMQR: A1 enters as the beta operand)
@@ -1504,6 +1518,8 @@ size_t qr_apply_workspace_bytes(const QrApplyDesc* descs, int n) {
 //                                         row block stops at its diagonal; the A1
 //                                         update rides in the epilogue)
 //   3. C2 -= V W2
+// A descriptor with notrans applies Q = I - V T V^T: its step 2 is W2 = T W, a
+// plain NN product (the zeros below T's diagonal take part), in the same launch.
 void launch_qr_apply(const QrApplyDesc* descs, int n, hipStream_t stream, double* ws) {
   if (n <= 0) return;
   std::vector<GemmDesc> g1, g2, g3;
@@ -1521,7 +1537,8 @@ void launch_qr_apply(const QrApplyDesc* descs, int n, hipStream_t stream, double
     g1.push_back(a);
     GemmDesc b{};
     b.A = d.T; b.lda = d.ldt; b.B = W; b.ldb = d.n; b.C = W2; b.ldc = d.n;
-    b.m = d.n; b.n = d.ncols; b.k = d.n; b.transA = 1; b.a_lower = 1; b.alpha = 1.0; b.beta = 0.0;
+    b.m = d.n; b.n = d.ncols; b.k = d.n; b.alpha = 1.0; b.beta = 0.0;
+    if (!d.notrans) { b.transA = 1; b.a_lower = 1; }
     if (d.A1) { b.C2 = d.A1; b.ldc2 = d.lda1; }
     g2.push_back(b);
     GemmDesc c{};
@@ -1571,4 +1588,8 @@ int parsec_amd_qr_apply(const parsec::QrApplyDesc* d, int n, void* ws, void* str
   return (int)hipGetLastError();
 }
 size_t parsec_amd_qr_apply_ws(const parsec::QrApplyDesc* d, int n) { return parsec::kern::qr_apply_workspace_bytes(d, n); }
+int parsec_amd_qr_extract_v(const double* A, int lda, int rows, int cols, double* Vout, void* stream) {
+  parsec::kern::launch_qr_extract_v(A, lda, rows, cols, Vout, (hipStream_t)stream);
+  return (int)hipGetLastError();
+}
 }

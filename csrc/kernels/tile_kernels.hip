@@ -729,6 +729,10 @@ __device__ __forceinline__ double rsqrt_nr(double d) {
   return y;
 }
 
+// kUpper (inverse only, factor == false): T is upper triangular; its transpose
+// is inverted with the same code and the result is written back transposed, so
+// invD holds T^-1 (upper). T's strict lower triangle is never read.
+template <bool kUpper = false>
 __device__ __forceinline__ void block_potrf64(double* T, int ldt, int w, double* invD, int* info, int info_base, bool factor) {
   __shared__ double Ls[64][65];      // Ls[c][r] = L(r, c)
   __shared__ double Xs[64][65];      // Xs[c][r] = X(r, c), X = L^-1
@@ -747,7 +751,10 @@ __device__ __forceinline__ void block_potrf64(double* T, int ldt, int w, double*
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int c = 16 * v + i;
-    a[i] = (r < w && c < w) ? T[(size_t)c * ldt + r] : (r == c ? 1.0 : 0.0);
+    if (kUpper)
+      a[i] = (r < w && c < w) ? (r >= c ? T[(size_t)r * ldt + c] : 0.0) : (r == c ? 1.0 : 0.0);
+    else
+      a[i] = (r < w && c < w) ? T[(size_t)c * ldt + r] : (r == c ? 1.0 : 0.0);
   }
   if (threadIdx.x == 0) bad_s = 0x7fffffff;
   __syncthreads();
@@ -856,7 +863,10 @@ __device__ __forceinline__ void block_potrf64(double* T, int ldt, int w, double*
 #pragma unroll
   for (int k = 0; k < 16; ++k) {
     const int c = 16 * v + k;
-    invD[(size_t)c * 64 + r] = Xs[c][r];
+    if (kUpper)
+      invD[(size_t)r * 64 + c] = Xs[c][r];
+    else
+      invD[(size_t)c * 64 + r] = Xs[c][r];
   }
 }
 
@@ -871,6 +881,13 @@ __global__ __launch_bounds__(kDiagThreads) void dtrtri_diag_kernel(const double*
   const int b = blockIdx.x;
   const int c0 = b * 64;
   block_potrf64(const_cast<double*>(L) + (size_t)c0 * ldl + c0, ldl, min(64, n - c0), invD + (size_t)b * 4096, nullptr, 0, false);
+}
+
+// The same for U (n x n upper): block b of invD is the (upper) inverse of U's block b.
+__global__ __launch_bounds__(kDiagThreads) void dtrtri_diag_upper_kernel(const double* U, int ldu, int n, double* invD) {
+  const int b = blockIdx.x;
+  const int c0 = b * 64;
+  block_potrf64<true>(const_cast<double*>(U) + (size_t)c0 * ldu + c0, ldu, min(64, n - c0), invD + (size_t)b * 4096, nullptr, 0, false);
 }
 
 // ==================================================================== TRSM
@@ -1032,6 +1049,12 @@ static_assert(sizeof(TrsmLeftArgs) <= 4096, "TrsmLeftArgs exceeds the kernel arg
 // L row / column lies past n reads the last valid one instead (finite data times
 // the zero padding, or a result row that is written back as zero). 8 waves: wave
 // (g, h) computes rows 16g..16g+15 of the block over half h of the reduction.
+// kUpper: L is upper triangular (U). op(U) = U couples block j with the blocks
+// below it, so trans 0 is the backward sweep and trans 1 (U^T, lower) the forward
+// one; the element op(U)(i, k) sits where op(L)(i, k) does, so only the
+// direction and the side that needs the clamp differ. Either way every element
+// read lies in the named triangle.
+template <bool kUpper>
 __global__ __launch_bounds__(kTrsmThreads) void dtrsm_left_kernel(const TrsmLeftArgs args) {
   extern __shared__ double P[];  // [rows padded][16], then red[16][64]
   PARSEC_WAVE_PRIO(args.prio);
@@ -1058,37 +1081,39 @@ __global__ __launch_bounds__(kTrsmThreads) void dtrsm_left_kernel(const TrsmLeft
     P[idx] = (i < n && j0 + jj < nrhs && alpha != 0.0) ? alpha * Bp[(size_t)(j0 + jj) * ldb + i] : 0.0;
   }
   __syncthreads();
+  const bool down = kUpper ? !tr : tr;  // backward sweep: blocks bottom up
   for (int s = 0; s < nblk; ++s) {
-    const int jb = tr ? nblk - 1 - s : s;
+    const int jb = down ? nblk - 1 - s : s;
     const int c0 = jb * 64;
-    const int cw = min(c0 + 16 * g + fr, n - 1);  // L row (forward) / column (backward) this lane feeds as the MFMA A-operand
+    const int cw = min(c0 + 16 * g + fr, n - 1);  // row (op N) / column (op T) of L this lane feeds as the MFMA A-operand
     double4_t acc[4];
 #pragma unroll
     for (int u = 0; u < 4; ++u) acc[u] = (double4_t){0.0, 0.0, 0.0, 0.0};
+    // the reduction runs over the solved blocks: above (forward) or below (backward)
+    const int kh = (down ? np - c0 - 64 : c0) / 2;  // multiple of 32
+    const int kbeg = (down ? c0 + 64 : 0) + h * kh, kend = kbeg + kh;
     if (!tr) {
       const double* __restrict__ Lp = L + cw;
-      const int kh = c0 / 2;  // multiple of 32
-      const int kbeg = h * kh, kend = kbeg + kh;
       for (int k = kbeg; k < kend; k += 16) {
         double av[4], bv[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          av[u] = Lp[(size_t)(k + 4 * u + fk) * ldl];
-          bv[u] = P[(k + 4 * u + fk) * 16 + fr];
+          const int kk = k + 4 * u + fk;
+          av[u] = Lp[(size_t)(kUpper ? min(kk, n - 1) : kk) * ldl];  // upper: columns >= n meet the strip's zero padding
+          bv[u] = P[kk * 16 + fr];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc[u], 0, 0, 0);
       }
     } else {
       const double* __restrict__ Lp = L + (size_t)cw * ldl;
-      const int kh = (np - c0 - 64) / 2;  // multiple of 32
-      const int kbeg = c0 + 64 + h * kh, kend = kbeg + kh;
       for (int k = kbeg; k < kend; k += 16) {
         double av[4], bv[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
-          av[u] = Lp[min(k + 4 * u + fk, n - 1)];  // rows >= n meet the strip's zero padding
-          bv[u] = P[(k + 4 * u + fk) * 16 + fr];
+          const int kk = k + 4 * u + fk;
+          av[u] = Lp[kUpper ? kk : min(kk, n - 1)];  // lower: rows >= n meet the strip's zero padding
+          bv[u] = P[kk * 16 + fr];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc[u], 0, 0, 0);
@@ -1497,61 +1522,88 @@ void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_
   hipLaunchKernelGGL(dtrtri_diag_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, L, ldl, n, invD);
 }
 
+void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipStream_t stream) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(dtrtri_diag_upper_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, U, ldu, n, invD);
+}
+
+// a matrix and the triangle of it that is solved with: the lower and the upper
+// triangle of one pointer are different matrices
+using TrsmLeftKey = std::pair<const double*, bool>;
+
 size_t trsm_left_workspace_bytes(const TrsmLeftDesc* descs, int n) {
   size_t bytes = 0;
-  std::vector<const double*> seen;
+  std::vector<TrsmLeftKey> seen;
   for (int i = 0; i < n; ++i) {
     if (descs[i].invD || descs[i].n <= 0) continue;
-    if (std::find(seen.begin(), seen.end(), descs[i].L) != seen.end()) continue;
-    seen.push_back(descs[i].L);
+    const TrsmLeftKey key{descs[i].L, descs[i].upper != 0};
+    if (std::find(seen.begin(), seen.end(), key) != seen.end()) continue;
+    seen.push_back(key);
     bytes += (size_t)((descs[i].n + 63) / 64) * 4096 * sizeof(double);
   }
   return bytes;
 }
 
 // Left-side solves, one workgroup per 16 columns of every B. Diagonal-block
-// inverses come from the descriptor or are computed once per distinct L into ws.
+// inverses come from the descriptor or are computed once per distinct (L,
+// triangle) into ws. The lower and the upper descriptors go to their own
+// instantiation of the kernel, each grouped 64 at a time in submission order.
 void launch_trsm_left_batch(const TrsmLeftDesc* descs, int n, hipStream_t stream, double* ws) {
   if (n <= 0) return;
   static bool attr = false;
   if (!attr) {
-    (void)hipFuncSetAttribute((const void*)dtrsm_left_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)dtrsm_left_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    (void)hipFuncSetAttribute((const void*)dtrsm_left_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     attr = true;
   }
-  std::vector<std::pair<const double*, const double*>> seen;  // L -> inverse blocks
+  std::vector<std::pair<TrsmLeftKey, const double*>> seen;  // (L, triangle) -> inverse blocks
   std::vector<const double*> inv(n, nullptr);
+  std::vector<int> order[2];  // descriptor indices per triangle
   size_t off = 0;
   for (int i = 0; i < n; ++i) {
+    const bool up = descs[i].upper != 0;
+    order[up].push_back(i);
     if (descs[i].n <= 0 || descs[i].nrhs <= 0) continue;
     if (descs[i].invD) { inv[i] = descs[i].invD; continue; }
-    auto it = std::find_if(seen.begin(), seen.end(), [&](const auto& e) { return e.first == descs[i].L; });
+    const TrsmLeftKey key{descs[i].L, up};
+    auto it = std::find_if(seen.begin(), seen.end(), [&](const auto& e) { return e.first == key; });
     if (it != seen.end()) { inv[i] = it->second; continue; }
     int nblk = (descs[i].n + 63) / 64;
     double* blk = ws + off;
     off += (size_t)nblk * 4096;
-    hipLaunchKernelGGL(dtrtri_diag_kernel, dim3(nblk), dim3(kDiagThreads), 0, stream, descs[i].L, descs[i].ldl, descs[i].n, blk);
-    seen.emplace_back(descs[i].L, blk);
+    if (up)
+      hipLaunchKernelGGL(dtrtri_diag_upper_kernel, dim3(nblk), dim3(kDiagThreads), 0, stream, descs[i].L, descs[i].ldl, descs[i].n, blk);
+    else
+      hipLaunchKernelGGL(dtrtri_diag_kernel, dim3(nblk), dim3(kDiagThreads), 0, stream, descs[i].L, descs[i].ldl, descs[i].n, blk);
+    seen.emplace_back(key, blk);
     inv[i] = blk;
   }
-  for (int s0 = 0; s0 < n; s0 += kMaxTrsmLeftBatch) {
-    const int cnt = std::min(kMaxTrsmLeftBatch, n - s0);
-    TrsmLeftArgs a;
-    a.count = cnt;
-    a.prio = t_launch_prio;
-    int total = 0, maxn = 0;
-    for (int i = 0; i < cnt; ++i) {
-      a.d[i] = descs[s0 + i];
-      a.d[i].invD = inv[s0 + i];
-      a.block_start[i] = total;
-      if (a.d[i].n <= 0 || a.d[i].nrhs <= 0) continue;
-      total += (a.d[i].nrhs + 15) / 16;
-      maxn = std::max(maxn, a.d[i].n);
+  for (int up = 0; up < 2; ++up) {
+    const std::vector<int>& idx = order[up];
+    const int nd = (int)idx.size();
+    for (int s0 = 0; s0 < nd; s0 += kMaxTrsmLeftBatch) {
+      const int cnt = std::min(kMaxTrsmLeftBatch, nd - s0);
+      TrsmLeftArgs a;
+      a.count = cnt;
+      a.prio = t_launch_prio;
+      int total = 0, maxn = 0;
+      for (int i = 0; i < cnt; ++i) {
+        a.d[i] = descs[idx[s0 + i]];
+        a.d[i].invD = inv[idx[s0 + i]];
+        a.block_start[i] = total;
+        if (a.d[i].n <= 0 || a.d[i].nrhs <= 0) continue;
+        total += (a.d[i].nrhs + 15) / 16;
+        maxn = std::max(maxn, a.d[i].n);
+      }
+      a.block_start[cnt] = total;
+      if (total == 0) continue;
+      if (maxn > kTrsmMaxCols) fatal("dtrsm left tile kernel: n=%d exceeds the LDS-resident strip limit %d", maxn, kTrsmMaxCols);
+      const size_t lds = ((size_t)((maxn + 63) / 64) * 64 * 16 + 1024) * sizeof(double);
+      if (up)
+        hipLaunchKernelGGL(dtrsm_left_kernel<true>, dim3(total), dim3(kTrsmThreads), lds, stream, a);
+      else
+        hipLaunchKernelGGL(dtrsm_left_kernel<false>, dim3(total), dim3(kTrsmThreads), lds, stream, a);
     }
-    a.block_start[cnt] = total;
-    if (total == 0) continue;
-    if (maxn > kTrsmMaxCols) fatal("dtrsm left tile kernel: n=%d exceeds the LDS-resident strip limit %d", maxn, kTrsmMaxCols);
-    const size_t lds = ((size_t)((maxn + 63) / 64) * 64 * 16 + 1024) * sizeof(double);
-    hipLaunchKernelGGL(dtrsm_left_kernel, dim3(total), dim3(kTrsmThreads), lds, stream, a);
   }
 }
 

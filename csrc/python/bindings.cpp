@@ -38,6 +38,7 @@ extern "C" int parsec_amd_qr_panel(const parsec::QrPanelDesc* d, int n, void* st
 extern "C" int parsec_amd_qr_profile(unsigned long long* out);
 extern "C" int parsec_amd_qr_apply(const parsec::QrApplyDesc* d, int n, void* ws, void* stream);
 extern "C" size_t parsec_amd_qr_apply_ws(const parsec::QrApplyDesc* d, int n);
+extern "C" int parsec_amd_qr_extract_v(const double* A, int lda, int rows, int cols, double* Vout, void* stream);
 namespace parsec { void register_builtin_dtd_gpu_bodies(); std::function<int(GpuExecContext*, Task*)> builtin_dtd_gpu_body(const std::string& name); }
 
 namespace {
@@ -531,6 +532,16 @@ PYBIND11_MODULE(_C, m) {
         return py::make_tuple(py::cast(tp, py::return_value_policy::reference), (uintptr_t)info);
       }, py::arg("uplo"), py::arg("A"), py::arg("B"),
       "Cholesky factorization then solve (lower, one rank); returns (taskpool, info address) or None. When info != 0 the solve does not run and B is untouched");
+  m.def("dormqr_new", [](int side, int trans, TiledMatrix* A, TiledMatrix* T, TiledMatrix* B) { return (Taskpool*)algos::dormqr_new(side, trans, A, T, B); },
+        py::arg("side"), py::arg("trans"), py::arg("A"), py::arg("T"), py::arg("B"), py::return_value_policy::reference,
+        "B := op(Q) B with the Q of dgeqrf_jdf_new / dgeqrf_new (not dgeqrf_hqr_new) in A and T: MATRIX_LEFT, MATRIX_TRANS or MATRIX_NOTRANS; B.mb must equal "
+        "A.mb; None for anything else. Release with taskpool_free");
+  m.def("dgeqrs_new", [](TiledMatrix* A, TiledMatrix* T, TiledMatrix* B) { return algos::dgeqrs_new(A, T, B); }, py::arg("A"), py::arg("T"), py::arg("B"),
+        py::return_value_policy::reference,
+        "least squares min ||A X - B||_F (M >= N) from the flat-tree QR factor in A and T: rows 0..N-1 of B := X, rows N.. the residual components; None on "
+        "invalid arguments. Release with taskpool_free");
+  m.def("dgels_new", [](TiledMatrix* A, TiledMatrix* T, TiledMatrix* B) { return algos::dgels_new(A, T, B); }, py::arg("A"), py::arg("T"), py::arg("B"),
+        py::return_value_policy::reference, "dgeqrf_jdf_new composed with dgeqrs_new; None on invalid arguments. Release with taskpool_free");
   m.def("dgeqrf_jdf_new", [](TiledMatrix* A, TiledMatrix* T) { return algos::dgeqrf_jdf_new(A, T); }, py::arg("A"), py::arg("T"),
         py::return_value_policy::take_ownership, "Tiled QR from the ptgpp-compiled dgeqrf.jdf (GEQRT / TSQRT / UNMQR / TSMQR)");
   m.def("dgeqrf_new", [](TiledMatrix* A, TiledMatrix* T, int ib) { return algos::dgeqrf_new(A, T, ib); }, py::arg("A"), py::arg("T"), py::arg("ib") = 0,
@@ -748,19 +759,27 @@ PYBIND11_MODULE(_C, m) {
     t.L = (const double*)L; t.B = (double*)B; t.m = mm; t.n = nn; t.ldl = ldl; t.ldb = ldb; t.trans = 1;
     return parsec_amd_dtrsm_batch(&t, 1, (void*)stream);
   });
-  m.def("kernel_dtrsm_left", [](uintptr_t L, uintptr_t B, int n, int nrhs, int ldl, int ldb, double alpha, int trans, uintptr_t stream) {
-    TrsmLeftDesc t{(const double*)L, (double*)B, n, nrhs, ldl, ldb, alpha, (uint8_t)(trans ? 1 : 0), nullptr};
+  m.def("kernel_dtrsm_left", [](uintptr_t L, uintptr_t B, int n, int nrhs, int ldl, int ldb, double alpha, int trans, uintptr_t stream, int upper) {
+    TrsmLeftDesc t{(const double*)L, (double*)B, n, nrhs, ldl, ldb, alpha, (uint8_t)(trans ? 1 : 0), (uint8_t)(upper ? 1 : 0), nullptr};
     return parsec_amd_dtrsm_left_batch(&t, 1, (void*)stream);
   }, py::arg("L"), py::arg("B"), py::arg("n"), py::arg("nrhs"), py::arg("ldl"), py::arg("ldb"), py::arg("alpha") = 1.0, py::arg("trans") = 0, py::arg("stream") = 0,
-     "B := alpha op(L)^-1 B on the GPU: L n x n lower (column-major, only the lower triangle is read), B n x nrhs; trans 1 solves with L^T");
-  // grouped launch: tuples (L, B, n, nrhs, ldl, ldb, alpha, trans)
-  m.def("kernel_dtrsm_left_batch", [](const std::vector<std::tuple<uintptr_t, uintptr_t, int, int, int, int, double, int>>& ds, uintptr_t stream) {
+     py::arg("upper") = 0,
+     "B := alpha op(L)^-1 B on the GPU: L n x n lower, or upper with upper=1 (column-major, only that triangle is read), B n x nrhs; trans 1 solves with L^T");
+  // grouped launch: tuples (L, B, n, nrhs, ldl, ldb, alpha, trans[, upper])
+  m.def("kernel_dtrsm_left_batch", [](const std::vector<py::tuple>& ds, uintptr_t stream) {
     std::vector<TrsmLeftDesc> v;
-    for (const auto& d : ds)
-      v.push_back(TrsmLeftDesc{(const double*)std::get<0>(d), (double*)std::get<1>(d), std::get<2>(d), std::get<3>(d), std::get<4>(d), std::get<5>(d),
-                               std::get<6>(d), (uint8_t)(std::get<7>(d) ? 1 : 0), nullptr});
+    for (const auto& d : ds) {
+      if (d.size() != 8 && d.size() != 9) throw std::invalid_argument("kernel_dtrsm_left_batch: tuples of (L, B, n, nrhs, ldl, ldb, alpha, trans[, upper])");
+      v.push_back(TrsmLeftDesc{(const double*)d[0].cast<uintptr_t>(), (double*)d[1].cast<uintptr_t>(), d[2].cast<int>(), d[3].cast<int>(), d[4].cast<int>(),
+                               d[5].cast<int>(), d[6].cast<double>(), (uint8_t)(d[7].cast<int>() ? 1 : 0),
+                               (uint8_t)(d.size() == 9 && d[8].cast<int>() ? 1 : 0), nullptr});
+    }
     return parsec_amd_dtrsm_left_batch(v.data(), (int)v.size(), (void*)stream);
   });
+  m.def("kernel_qr_extract_v", [](uintptr_t A, int lda, int rows, int cols, uintptr_t Vout, uintptr_t stream) {
+    return parsec_amd_qr_extract_v((const double*)A, lda, rows, cols, (double*)Vout, (void*)stream);
+  }, py::arg("A"), py::arg("lda"), py::arg("rows"), py::arg("cols"), py::arg("Vout"), py::arg("stream") = 0,
+     "Vout (rows x min(rows, cols), ld rows) := the clean unit-lower V of a factored QR diagonal tile A");
   m.def("kernel_qr_panel", [](uintptr_t A1, int lda1, uintptr_t A2, int lda2, uintptr_t T, int ldt, uintptr_t V, int m1, int m2, int n, uintptr_t stream) {
     QrPanelDesc q{};
     q.A1 = (double*)A1; q.lda1 = lda1; q.A2 = (double*)A2; q.lda2 = lda2; q.T = (double*)T; q.ldt = ldt; q.Vcopy = (double*)V;
@@ -776,6 +795,13 @@ PYBIND11_MODULE(_C, m) {
     QrApplyDesc q{};
     q.V = (const double*)V; q.ldv = ldv; q.T = (const double*)T; q.ldt = ldt; q.A1 = (double*)A1; q.lda1 = lda1; q.A2 = (double*)A2; q.lda2 = lda2;
     q.m2 = m2; q.n = n; q.ncols = ncols;
+    return parsec_amd_qr_apply(&q, 1, (void*)ws, (void*)stream);
+  });
+  // the same with the op as a last argument: notrans 1 applies Q, 0 Q^T
+  m.def("kernel_qr_apply", [](uintptr_t V, int ldv, uintptr_t T, int ldt, uintptr_t A1, int lda1, uintptr_t A2, int lda2, int m2, int n, int ncols, uintptr_t ws, uintptr_t stream, int notrans) {
+    QrApplyDesc q{};
+    q.V = (const double*)V; q.ldv = ldv; q.T = (const double*)T; q.ldt = ldt; q.A1 = (double*)A1; q.lda1 = lda1; q.A2 = (double*)A2; q.lda2 = lda2;
+    q.m2 = m2; q.n = n; q.ncols = ncols; q.notrans = notrans ? 1 : 0;
     return parsec_amd_qr_apply(&q, 1, (void*)ws, (void*)stream);
   });
   // batched block-reflector applications (one grouped launch per GEMM phase):

@@ -676,6 +676,23 @@ parsec_taskpool_t* parsec_dpotrs_New(parsec_matrix_uplo_t uplo, parsec_tiled_mat
  * factorization fails (*info != 0) the solve does not run and B is untouched.
  * One rank only: NULL on more (factor, check info, then parsec_dpotrs_New). */
 parsec_taskpool_t* parsec_dposv_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info);
+/* Least squares with the tile QR factor (DPLASMA's dplasma_dormqr_New /
+ * dgeqrs / dgels roles; the ptgpp-compiled dormqr.jdf and dtrsm_LU.jdf). A is
+ * M x N with square tiles, T (tiled like A) holds the block reflectors, B is
+ * M x NRHS with B->mb == A->mb; A / T and B may be distributed on different
+ * process grids. The factor must come from the flat-tree QR (parsec_dgels_New
+ * itself, or the library's dgeqrf taskpools), not from the hierarchical one.
+ * parsec_dormqr_New: B := op(Q) B, PARSEC_MATRIX_LEFT with PARSEC_MATRIX_TRANS
+ * or PARSEC_MATRIX_NOTRANS. parsec_dgeqrs_New (M >= N): rows 0..N-1 of B become
+ * the minimiser X of ||A X - B||_F, rows N..M-1 the residual components (their
+ * column norms are the residual norms); a singular R gives inf / nan.
+ * parsec_dgels_New: the QR factorization of A (into A and T), then dgeqrs. All
+ * return NULL (after a warning) for any other request or shape; release with
+ * parsec_taskpool_free. */
+parsec_taskpool_t* parsec_dormqr_New(parsec_matrix_side_t side, parsec_matrix_trans_t trans, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* T,
+                                     parsec_tiled_matrix_t* B);
+parsec_taskpool_t* parsec_dgeqrs_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* T, parsec_tiled_matrix_t* B);
+parsec_taskpool_t* parsec_dgels_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* T, parsec_tiled_matrix_t* B);
 int parsec_apply(parsec_context_t* parsec, parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_unary_op_t operation, void* op_args);
 /* op(es, src_tile, dest_tile, op_data, m, n) for every tile of dest */
 parsec_taskpool_t* parsec_map_operator_New(const parsec_tiled_matrix_t* src, parsec_tiled_matrix_t* dest, parsec_operator_t op, void* op_data);
