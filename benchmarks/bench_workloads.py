@@ -18,6 +18,12 @@
            2 M N^2 - 2/3 N^3 for DGELS); the same process then times a torch
            yardstick on the dense data: torch.linalg.lstsq if it runs on the
            device, otherwise torch.linalg.qr + solve_triangular
+  getrf    LU WITHOUT pivoting on a seeded, column diagonally dominant matrix:
+           DGETRF_NOPIV alone (2/3 N^3) and DGESV_NOPIV (+ 2 N^2 NRHS), A (and
+           B) restored every timed step, with the backward error
+           ||L U - A||_F / ||A||_F; the same process then times
+           torch.linalg.lu_factor / lu_solve on the dense data -- torch PIVOTS
+           (partial pivoting), so the yardstick does more work than we do
 
 Multi-GPU: launch like bench.py (torch.distributed.run, one rank per GPU).
 
@@ -26,6 +32,7 @@ Multi-GPU: launch like bench.py (torch.distributed.run, one rank per GPU).
     python benchmarks/bench_workloads.py dtd_gemm --n 2048
     python benchmarks/bench_workloads.py potrs --n 16384 --nb 512 --nrhs 16384
     python benchmarks/bench_workloads.py gels --m 32768 --n 8192 --nb 512 --nrhs 512
+    python benchmarks/bench_workloads.py getrf --n 16384 --nb 512 --nrhs 512
 """
 import argparse
 import json
@@ -475,15 +482,141 @@ def bench_gels(args):
     return out, 0
 
 
+def bench_getrf(args):
+    import torch
+
+    import parsec_amd as pa
+
+    world, rank, local = _dist()
+    if world > 1:
+        raise RuntimeError("getrf: one GPU (the yardstick is a single-device torch.linalg.lu_factor)")
+    if not torch.cuda.is_available():
+        raise RuntimeError("getrf: no GPU")
+    N, nb, NRHS = args.n, args.nb, args.nrhs
+    nbr = args.nbr or min(nb, NRHS)
+    dev = torch.device("cuda", 0)
+    ctx = pa.init(args.cores)
+    gpu = pa.first_gpu_device_index()
+    if gpu < 0:
+        raise RuntimeError("no GPU device registered in the runtime")
+    NT, NTB = -(-N // nb), -(-NRHS // nbr)
+
+    def run(tp):
+        ctx.add_taskpool(tp)
+        ctx.start()
+        ctx.wait()
+
+    def tiled(dense, rows, cols, mt, nt, mb, cb):  # the store image [n][m][col][row] of a dense matrix
+        pad = torch.zeros((mt * mb, nt * cb), dtype=torch.float64, device=dev)
+        pad[:rows, :cols] = dense
+        return pad.reshape(mt, mb, nt, cb).permute(2, 0, 3, 1).contiguous()
+
+    def dense_of(store, rows, cols, mb, cb):  # a dense COPY of a tiled store
+        return store.permute(1, 3, 0, 2).reshape(store.shape[1] * mb, store.shape[0] * cb)[:rows, :cols].contiguous()
+
+    # R standard normal + diag(column sums of |R| + 1): column diagonally dominant,
+    # the class of matrices an unpivoted LU is meant for
+    gen = torch.Generator(device=dev).manual_seed(12345)
+    S = torch.randn((N, N), dtype=torch.float64, device=dev, generator=gen)
+    S += torch.diag(S.abs().sum(dim=0) + 1.0)
+    B0 = torch.randn((N, NRHS), dtype=torch.float64, device=dev, generator=gen)
+    backupA = tiled(S, N, N, NT, NT, nb, nb)
+    backupB = tiled(B0, N, NRHS, NT, NTB, nb, nbr)
+    sa = backupA.clone()
+    sb = backupB.clone()
+    A = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nb, N, N, device=gpu, ptr=sa.data_ptr())
+    B = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nbr, N, NRHS, device=gpu, ptr=sb.data_ptr())
+    torch.cuda.synchronize()
+    infos = []
+
+    def step_getrf():
+        sa.copy_(backupA)
+        torch.cuda.synchronize()
+        tp, info = pa.dgetrf_nopiv_new(A)
+        run(tp)
+        infos.append(pa.read_int(info))
+
+    def step_gesv():
+        sa.copy_(backupA)
+        sb.copy_(backupB)
+        torch.cuda.synchronize()
+        tp, info = pa.dgesv_nopiv_new(A, B)
+        run(tp)
+        infos.append(pa.read_int(info))
+        pa.taskpool_free(tp)
+
+    def timed(step):
+        for _ in range(args.warmup):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps
+
+    dt_getrf = timed(step_getrf)
+    F = dense_of(sa, N, N, nb, nb)
+    L = torch.tril(F, -1)
+    L.diagonal().fill_(1.0)
+    nS = torch.linalg.norm(S)
+    lu_bwd = float(torch.linalg.norm(L @ torch.triu(F) - S) / nS)
+    del L, F
+    dt_gesv = timed(step_gesv)
+    if any(infos):
+        raise RuntimeError(f"a zero pivot was reported: info {infos}")
+    X = dense_of(sb, N, NRHS, nb, nbr)
+    resid = float(torch.linalg.norm(S @ X - B0) / (nS * torch.linalg.norm(X) + torch.linalg.norm(B0)))
+    if not (lu_bwd < 1e-13 and resid < 1e-13):
+        raise RuntimeError(f"backward error too large: LU {lu_bwd:.3e}, solve {resid:.3e}")
+    flops_lu = 2.0 / 3.0 * N ** 3
+    flops_sv = flops_lu + 2.0 * N * N * NRHS
+    del sa, backupA
+    # yardstick on the dense data: torch's LU, which PIVOTS (out of place, no restore needed)
+    for _ in range(max(1, args.warmup)):
+        LU, piv = torch.linalg.lu_factor(S)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        LU, piv = torch.linalg.lu_factor(S)
+    torch.cuda.synchronize()
+    dty_lu = (time.perf_counter() - t0) / args.steps
+    for _ in range(max(1, args.warmup)):
+        Y = torch.linalg.lu_solve(LU, piv, B0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        Y = torch.linalg.lu_solve(LU, piv, B0)
+    torch.cuda.synchronize()
+    dty_sv = dty_lu + (time.perf_counter() - t0) / args.steps
+    swaps = int((piv != torch.arange(1, N + 1, device=dev, dtype=piv.dtype)).sum())
+    Lt = torch.tril(LU, -1)
+    Lt.diagonal().fill_(1.0)
+    torch_bwd = float(torch.linalg.norm(Lt @ torch.triu(LU) - S) / nS) if swaps == 0 else None
+    diff = float(torch.linalg.norm(X - Y) / torch.linalg.norm(Y))
+    ctx.fini()
+    out = {"metric": "GFLOP/s DGETRF_NOPIV (dgetrf_nopiv.jdf, no pivoting, HBM-resident tiles, A restored every step)", "value": round(flops_lu / dt_getrf / 1e9, 1),
+           "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt_getrf * 1e3, 3), "higher_is_better": True,
+           "dtype": "fp64", "flops_getrf": flops_lu, "flops_gesv": flops_sv, "lu_backward_error": lu_bwd,
+           "dgesv_gflops": round(flops_sv / dt_gesv / 1e9, 1), "dgesv_ms": round(dt_gesv * 1e3, 3), "dgesv_backward_error": resid,
+           "yardstick": "torch.linalg.lu_factor / lu_solve on the dense data, same process; torch PIVOTS (partial pivoting), we do not",
+           "yardstick_lu_gflops": round(flops_lu / dty_lu / 1e9, 1), "yardstick_lu_ms": round(dty_lu * 1e3, 3),
+           "yardstick_solve_gflops": round(flops_sv / dty_sv / 1e9, 1), "yardstick_solve_ms": round(dty_sv * 1e3, 3),
+           "yardstick_row_swaps": swaps, "yardstick_lu_backward_error": torch_bwd,
+           "ratio_to_yardstick": round(dty_lu / dt_getrf, 3), "dgesv_ratio_to_yardstick": round(dty_sv / dt_gesv, 3), "rel_diff_to_yardstick": diff,
+           "config": {"model": "DGETRF_NOPIV", "N": N, "nb": nb, "NRHS": NRHS, "nbr": nbr, "cores": args.cores}}
+    return out, 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm", "potrs", "gels"])
+    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm", "potrs", "gels", "getrf"])
     ap.add_argument("--n", "--size", dest="n", type=int, default=None, help="matrix order (use --size under torchrun)")
     ap.add_argument("--m", type=int, default=None, help="gels: rows of A (default: n)")
     ap.add_argument("--nb", type=int, default=512)
     ap.add_argument("--ib", type=int, default=32, help="qr: accepted for the reference's command line; both taskpools factor 32-column sub-panels (qr_sub2c) and apply one nb x nb block reflector per tile")
-    ap.add_argument("--nrhs", type=int, default=None, help="potrs / gels: right-hand sides (default: n)")
-    ap.add_argument("--nbr", type=int, default=0, help="potrs / gels: tile width of B (default: min(nb, nrhs))")
+    ap.add_argument("--nrhs", type=int, default=None, help="potrs / gels / getrf: right-hand sides (default: n)")
+    ap.add_argument("--nbr", type=int, default=0, help="potrs / gels / getrf: tile width of B (default: min(nb, nrhs))")
     ap.add_argument("--b", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=2)
@@ -498,12 +631,12 @@ def main():
                     help="qr: rows per TS domain of the hierarchical tree (0: one flat TS chain per process row, TT binary tree across process rows; 1 GPU measured fastest flat: profiles/r3_qr_tree_ab.jsonl)")
     args = ap.parse_args()
     if args.n is None:
-        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048, "potrs": 16384, "gels": 16384}[args.workload]
+        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048, "potrs": 16384, "gels": 16384, "getrf": 16384}[args.workload]
     if args.nrhs is None:
         args.nrhs = args.n
     if args.m is None:
         args.m = args.n
-    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm, "potrs": bench_potrs, "gels": bench_gels}[args.workload]
+    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm, "potrs": bench_potrs, "gels": bench_gels, "getrf": bench_getrf}[args.workload]
     out, rank = fn(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -32,6 +32,25 @@ Taskpool* dpotrs_new(int uplo, TiledMatrix* A, TiledMatrix* B);
 // untouched. One rank only (nullptr otherwise): ranks see only the pivots of
 // their own diagonal tiles.
 Taskpool* dposv_new(int uplo, TiledMatrix* A, TiledMatrix* B, int* info);
+// Tiled LU factorization WITHOUT pivoting, A = L U, from the JDF source
+// algos/jdf/dgetrf_nopiv.jdf: A is square (M == N) with square tiles, double; a
+// ragged last tile is allowed. On return A holds L (unit lower, its diagonal not
+// stored) and U. The matrix must not need pivoting (diagonally dominant, or
+// preconditioned): `info_host` receives the 1-based global index of the first
+// pivot that is exactly zero (0 = none); a merely small pivot is not reported.
+// Anything else returns nullptr after a warning.
+ptg::PtgTaskpool* dgetrf_nopiv_new(TiledMatrix* A, int* info_host);
+// Solve op(A) X = B with the factor dgetrf_nopiv_new left in A: trans NoTrans
+// (the unit L sweep of dtrsm_LL.jdf, then the U sweep of dtrsm_LU.jdf) or Trans
+// (U^T, then L^T). B is N x NRHS with B->mb == A->nb, any tile width, any
+// distribution, and is overwritten with X. Freeing the returned taskpool
+// (taskpool_free) frees the two sweeps.
+Taskpool* dgetrs_nopiv_new(int trans, TiledMatrix* A, TiledMatrix* B);
+// dgetrf_nopiv_new composed with dgetrs_nopiv_new (NoTrans). When the
+// factorization meets a zero pivot (*info != 0 once it completed) the solve
+// taskpools start empty: B is left untouched. `info` is required. One rank only
+// (nullptr otherwise): ranks see only the pivots of their own diagonal tiles.
+Taskpool* dgesv_nopiv_new(TiledMatrix* A, TiledMatrix* B, int* info);
 // Tiled GEMM C = alpha op(A) op(B) + beta C (PTG; B transposed if transB).
 ptg::PtgTaskpool* dgemm_new(double alpha, TiledMatrix* A, TiledMatrix* B, double beta, TiledMatrix* C, int transB);
 // Tiled QR A = QR (Householder, tile algorithm GEQRT/TSQRT/UNMQR/TSMQR). T holds

@@ -1139,6 +1139,13 @@ parsec_taskpool_t* parsec_dgeqrs_New(parsec_tiled_matrix_t* A, parsec_tiled_matr
 parsec_taskpool_t* parsec_dgels_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* T, parsec_tiled_matrix_t* B) {
   return algos::dgels_new(tm_of(A), tm_of(T), tm_of(B));
 }
+parsec_taskpool_t* parsec_dgetrf_nopiv_New(parsec_tiled_matrix_t* A, int* info) { return algos::dgetrf_nopiv_new(tm_of(A), info); }
+parsec_taskpool_t* parsec_dgetrs_nopiv_New(parsec_matrix_trans_t trans, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B) {
+  return algos::dgetrs_nopiv_new((int)trans, tm_of(A), tm_of(B));
+}
+parsec_taskpool_t* parsec_dgesv_nopiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info) {
+  return algos::dgesv_nopiv_new(tm_of(A), tm_of(B), info);
+}
 int parsec_apply(parsec_context_t* parsec, parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_unary_op_t operation, void* op_args) {
   parsec_taskpool_t* tp = parsec_apply_New(uplo, A, operation, op_args);
   parsec_context_add_taskpool(parsec, tp);

@@ -127,9 +127,10 @@ struct TrsmDesc {  // B := B * op(L)^-1 ; right side, lower, (trans), non-unit
   const double* invD = nullptr;  // optional: inverses of L's 64x64 diagonal blocks (from POTRF)
   const double* gate_slot = nullptr;  // gate: max|L|, max|W| of the panel (workspace)
 };
-// B := alpha * op(L)^-1 B ; left side, non-unit, L lower (default) or upper. L
-// is n x n column-major and only the named triangle is read (the other one may
-// hold anything: the V of a QR diagonal tile), B is n x nrhs.
+// B := alpha * op(L)^-1 B ; left side, L lower (default) or upper. L is n x n
+// column-major and only the named triangle is read (the other one may hold
+// anything: the V of a QR diagonal tile, the other factor of an LU tile), B is
+// n x nrhs. With `right`, B is nrhs x n and X op(L) = alpha B is solved instead.
 struct TrsmLeftDesc {
   const double* L;
   double* B;
@@ -138,10 +139,16 @@ struct TrsmLeftDesc {
   double alpha;
   uint8_t trans;  // 0: L^-1 B (lower: forward sweep, upper: backward), 1: L^-T B (the other direction)
   uint8_t upper = 0;  // 1: L is upper triangular (the R of a QR factor)
+  uint8_t unit = 0;   // 1: the diagonal of L is taken as 1 and never read (the L of an LU factor)
+  // 1: right side, B := alpha B op(L)^-1 with B nrhs x n (n stays the order of
+  // L, nrhs is the number of ROWS of B): op(L)^T X^T = alpha B^T, the same sweep
+  // with the transpose flipped and the strip loaded and stored transposed
+  uint8_t right = 0;
   // optional: inverses of L's 64x64 diagonal blocks (of the same triangle),
   // contiguous 4096-double blocks (dtrtri_diag_kernel / dtrtri_diag_upper_kernel)
   const double* invD = nullptr;
 };
+static_assert(sizeof(TrsmLeftDesc) == 56, "TrsmLeftDesc grew: the left-solve kernel argument block is sized for 64 of them");
 static_assert(sizeof(GemmDesc) == 96, "GemmDesc grew: the grouped-GEMM kernel argument block is sized for 40 of them");
 
 struct PotrfDesc {
@@ -155,6 +162,24 @@ struct PotrfDesc {
   // zeros (W lower incl. the diagonal, L(i, j) = W_out(j, i) for i > j), so the
   // panel solve needs this ONE tile (TrsmGemmDesc::packed)
   uint8_t pack_w = 0;
+};
+
+// LU factorization without pivoting of an n x n tile (1 <= n <= 1152, lda >= n):
+// A := L\U, L unit lower (its diagonal is not stored), U upper. Nothing outside
+// the n x n part is read or written. *info (optional) receives info_base + the
+// 1-based index of the first pivot that is exactly zero (the smallest index
+// wins, the word is left alone otherwise); the factorization still finishes and
+// then holds inf / nan. No pivoting: the matrix must not need it.
+struct GetrfDesc {
+  double* A;
+  int n, lda;
+  int* info;  // device pointer (may be null)
+  // optional: the inverses of the 64 x 64 diagonal blocks of L (unit lower) and
+  // of U, ceil(n/64) x 4096 doubles each, in the layout of dtrtri_diag_kernel /
+  // dtrtri_diag_upper_kernel (identity-padded in a ragged last block)
+  double* invL_out = nullptr;
+  double* invU_out = nullptr;
+  int info_base = 0;  // added to the index reported (the tile's first row in the matrix)
 };
 
 // Panel solve through the explicit inverse: B := B * W^T with W = L^-1 from
@@ -181,10 +206,14 @@ double trsm_inverse_limit();
 namespace kern {
 // Inverses of the 64 x 64 diagonal blocks of L (n x n lower, ld ldl) into invD:
 // block b at invD + b * 4096, column-major, padded with the identity
-void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream);
+// (unit: L's diagonal is taken as 1 and never read)
+void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream, bool unit = false);
 // the same for U (n x n upper): the blocks of invD are upper triangular; U's
 // strict lower triangle is never read
-void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipStream_t stream);
+void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipStream_t stream, bool unit = false);
+// tile LU without pivoting; ws: getrf_workspace_bytes(g)
+void launch_getrf_nopiv(const GetrfDesc& g, hipStream_t stream, double* ws);
+size_t getrf_workspace_bytes(const GetrfDesc& g);
 // Vout (rows x min(rows, cols), ld rows) := the unit-lower V stored below the
 // diagonal of a factored QR diagonal tile A (ld lda): ones on the diagonal,
 // zeros above (the layout of QrPanelDesc::Vcopy)
@@ -265,6 +294,7 @@ struct KernelBatch {
   std::vector<TrsmDesc> trsm;
   std::vector<TrsmLeftDesc> trsm_left;
   std::vector<PotrfDesc> potrf;
+  std::vector<GetrfDesc> getrf;
   std::vector<TrsmGemmDesc> trsm_w;
   std::vector<StencilDesc> stencil;
   std::vector<QrPanelDesc> qr_panel;
@@ -277,8 +307,8 @@ struct KernelBatch {
   // (kernels: g_crit_cu, bulk_yield) so the chain runs at idle speed
   int claim_cus = 0;  // 1: tile-POTRF steps claim, 2: every kernel of the launch
   bool bulk_yield = false;  // bulk launch: poll the claims
-  bool empty() const { return pre_gemm.empty() && gemm.empty() && trsm.empty() && trsm_left.empty() && potrf.empty() && trsm_w.empty() && stencil.empty() && qr_panel.empty() && qr_apply.empty() && generic.empty(); }
-  void clear() { pre_gemm.clear(); gemm.clear(); trsm.clear(); trsm_left.clear(); potrf.clear(); trsm_w.clear(); stencil.clear(); qr_panel.clear(); qr_apply.clear(); generic.clear(); }
+  bool empty() const { return pre_gemm.empty() && gemm.empty() && trsm.empty() && trsm_left.empty() && potrf.empty() && getrf.empty() && trsm_w.empty() && stencil.empty() && qr_panel.empty() && qr_apply.empty() && generic.empty(); }
+  void clear() { pre_gemm.clear(); gemm.clear(); trsm.clear(); trsm_left.clear(); potrf.clear(); getrf.clear(); trsm_w.clear(); stencil.clear(); qr_panel.clear(); qr_apply.clear(); generic.clear(); }
 };
 
 struct HipDevice;

@@ -732,7 +732,8 @@ __device__ __forceinline__ double rsqrt_nr(double d) {
 // kUpper (inverse only, factor == false): T is upper triangular; its transpose
 // is inverted with the same code and the result is written back transposed, so
 // invD holds T^-1 (upper). T's strict lower triangle is never read.
-template <bool kUpper = false>
+// kUnit (inverse only): T's diagonal is taken as 1 and never read.
+template <bool kUpper = false, bool kUnit = false>
 __device__ __forceinline__ void block_potrf64(double* T, int ldt, int w, double* invD, int* info, int info_base, bool factor) {
   __shared__ double Ls[64][65];      // Ls[c][r] = L(r, c)
   __shared__ double Xs[64][65];      // Xs[c][r] = X(r, c), X = L^-1
@@ -752,9 +753,9 @@ __device__ __forceinline__ void block_potrf64(double* T, int ldt, int w, double*
   for (int i = 0; i < 16; ++i) {
     const int c = 16 * v + i;
     if (kUpper)
-      a[i] = (r < w && c < w) ? (r >= c ? T[(size_t)r * ldt + c] : 0.0) : (r == c ? 1.0 : 0.0);
+      a[i] = (r < w && c < w && !(kUnit && r == c)) ? (r >= c ? T[(size_t)r * ldt + c] : 0.0) : (r == c ? 1.0 : 0.0);
     else
-      a[i] = (r < w && c < w) ? T[(size_t)c * ldt + r] : (r == c ? 1.0 : 0.0);
+      a[i] = (r < w && c < w && !(kUnit && r == c)) ? T[(size_t)c * ldt + r] : (r == c ? 1.0 : 0.0);
   }
   if (threadIdx.x == 0) bad_s = 0x7fffffff;
   __syncthreads();
@@ -888,6 +889,19 @@ __global__ __launch_bounds__(kDiagThreads) void dtrtri_diag_upper_kernel(const d
   const int b = blockIdx.x;
   const int c0 = b * 64;
   block_potrf64<true>(const_cast<double*>(U) + (size_t)c0 * ldu + c0, ldu, min(64, n - c0), invD + (size_t)b * 4096, nullptr, 0, false);
+}
+
+// The unit-diagonal variants: the diagonal of L / U is taken as 1 and never read
+// (the L of an LU factor shares its tile with U, whose diagonal sits there).
+__global__ __launch_bounds__(kDiagThreads) void dtrtri_diag_unit_kernel(const double* L, int ldl, int n, double* invD) {
+  const int b = blockIdx.x;
+  const int c0 = b * 64;
+  block_potrf64<false, true>(const_cast<double*>(L) + (size_t)c0 * ldl + c0, ldl, min(64, n - c0), invD + (size_t)b * 4096, nullptr, 0, false);
+}
+__global__ __launch_bounds__(kDiagThreads) void dtrtri_diag_upper_unit_kernel(const double* U, int ldu, int n, double* invD) {
+  const int b = blockIdx.x;
+  const int c0 = b * 64;
+  block_potrf64<true, true>(const_cast<double*>(U) + (size_t)c0 * ldu + c0, ldu, min(64, n - c0), invD + (size_t)b * 4096, nullptr, 0, false);
 }
 
 // ==================================================================== TRSM
@@ -1054,6 +1068,12 @@ static_assert(sizeof(TrsmLeftArgs) <= 4096, "TrsmLeftArgs exceeds the kernel arg
 // one; the element op(U)(i, k) sits where op(L)(i, k) does, so only the
 // direction and the side that needs the clamp differ. Either way every element
 // read lies in the named triangle.
+// TrsmLeftDesc::right: B is nrhs x n and X op(L) = alpha B, i.e. op(L)^T X^T =
+// alpha B^T: the same sweep with the transpose flipped on the strip of B^T. A
+// workgroup then owns 16 ROWS of B, LDS element [i][jj] is B[i * ldb + j0 + jj]
+// (128 contiguous bytes per column of B); only the two strip loops differ.
+// TrsmLeftDesc::unit is the launcher's business alone: the kernel reads diagonal
+// blocks only through invD.
 template <bool kUpper>
 __global__ __launch_bounds__(kTrsmThreads) void dtrsm_left_kernel(const TrsmLeftArgs args) {
   extern __shared__ double P[];  // [rows padded][16], then red[16][64]
@@ -1066,7 +1086,8 @@ __global__ __launch_bounds__(kTrsmThreads) void dtrsm_left_kernel(const TrsmLeft
   const int nblk = (n + 63) / 64;
   const int np = nblk * 64;
   double* red = P + np * 16;
-  const bool tr = d.trans != 0;
+  const bool right = d.right != 0;
+  const bool tr = (d.trans != 0) != right;
   const double alpha = d.alpha;
   double* Bp = d.B;
   const size_t ldb = d.ldb;
@@ -1076,9 +1097,16 @@ __global__ __launch_bounds__(kTrsmThreads) void dtrsm_left_kernel(const TrsmLeft
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const int g = wv & 3, h = wv >> 2;
   const int fr = lane & 15, fk = lane >> 4;
-  for (int idx = tid; idx < np * 16; idx += kTrsmThreads) {
-    const int i = idx >> 4, jj = idx & 15;
-    P[idx] = (i < n && j0 + jj < nrhs && alpha != 0.0) ? alpha * Bp[(size_t)(j0 + jj) * ldb + i] : 0.0;
+  if (!right) {
+    for (int idx = tid; idx < np * 16; idx += kTrsmThreads) {
+      const int i = idx >> 4, jj = idx & 15;
+      P[idx] = (i < n && j0 + jj < nrhs && alpha != 0.0) ? alpha * Bp[(size_t)(j0 + jj) * ldb + i] : 0.0;
+    }
+  } else {
+    for (int idx = tid; idx < np * 16; idx += kTrsmThreads) {
+      const int i = idx >> 4, jj = idx & 15;
+      P[idx] = (i < n && j0 + jj < nrhs && alpha != 0.0) ? alpha * Bp[(size_t)i * ldb + j0 + jj] : 0.0;
+    }
   }
   __syncthreads();
   const bool down = kUpper ? !tr : tr;  // backward sweep: blocks bottom up
@@ -1159,9 +1187,16 @@ __global__ __launch_bounds__(kTrsmThreads) void dtrsm_left_kernel(const TrsmLeft
     }
     __syncthreads();
   }
-  for (int idx = tid; idx < n * 16; idx += kTrsmThreads) {
-    const int i = idx >> 4, jj = idx & 15;
-    if (j0 + jj < nrhs) Bp[(size_t)(j0 + jj) * ldb + i] = P[idx];
+  if (!right) {
+    for (int idx = tid; idx < n * 16; idx += kTrsmThreads) {
+      const int i = idx >> 4, jj = idx & 15;
+      if (j0 + jj < nrhs) Bp[(size_t)(j0 + jj) * ldb + i] = P[idx];
+    }
+  } else {
+    for (int idx = tid; idx < n * 16; idx += kTrsmThreads) {
+      const int i = idx >> 4, jj = idx & 15;
+      if (j0 + jj < nrhs) Bp[(size_t)i * ldb + j0 + jj] = P[idx];
+    }
   }
 }
 
@@ -1517,26 +1552,35 @@ void launch_trsm_batch(const TrsmDesc* descs, int n, hipStream_t stream, double*
   launch_trsm_inv(descs, inv.data(), n, stream);
 }
 
-void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream) {
+void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream, bool unit) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(dtrtri_diag_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, L, ldl, n, invD);
+  if (unit)
+    hipLaunchKernelGGL(dtrtri_diag_unit_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, L, ldl, n, invD);
+  else
+    hipLaunchKernelGGL(dtrtri_diag_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, L, ldl, n, invD);
 }
 
-void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipStream_t stream) {
+void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipStream_t stream, bool unit) {
   if (n <= 0) return;
-  hipLaunchKernelGGL(dtrtri_diag_upper_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, U, ldu, n, invD);
+  if (unit)
+    hipLaunchKernelGGL(dtrtri_diag_upper_unit_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, U, ldu, n, invD);
+  else
+    hipLaunchKernelGGL(dtrtri_diag_upper_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, U, ldu, n, invD);
 }
 
 // a matrix and the triangle of it that is solved with: the lower and the upper
-// triangle of one pointer are different matrices
-using TrsmLeftKey = std::pair<const double*, bool>;
+// triangle of one pointer are different matrices, and so are the unit and the
+// non-unit reading of one triangle (bit 0: upper, bit 1: unit). The side is not
+// part of it: a right-side solve uses the same inverses.
+using TrsmLeftKey = std::pair<const double*, int>;
+static inline TrsmLeftKey trsm_left_key(const TrsmLeftDesc& d) { return {d.L, (d.upper ? 1 : 0) | (d.unit ? 2 : 0)}; }
 
 size_t trsm_left_workspace_bytes(const TrsmLeftDesc* descs, int n) {
   size_t bytes = 0;
   std::vector<TrsmLeftKey> seen;
   for (int i = 0; i < n; ++i) {
     if (descs[i].invD || descs[i].n <= 0) continue;
-    const TrsmLeftKey key{descs[i].L, descs[i].upper != 0};
+    const TrsmLeftKey key = trsm_left_key(descs[i]);
     if (std::find(seen.begin(), seen.end(), key) != seen.end()) continue;
     seen.push_back(key);
     bytes += (size_t)((descs[i].n + 63) / 64) * 4096 * sizeof(double);
@@ -1546,7 +1590,7 @@ size_t trsm_left_workspace_bytes(const TrsmLeftDesc* descs, int n) {
 
 // Left-side solves, one workgroup per 16 columns of every B. Diagonal-block
 // inverses come from the descriptor or are computed once per distinct (L,
-// triangle) into ws. The lower and the upper descriptors go to their own
+// triangle, unit) into ws. The lower and the upper descriptors go to their own
 // instantiation of the kernel, each grouped 64 at a time in submission order.
 void launch_trsm_left_batch(const TrsmLeftDesc* descs, int n, hipStream_t stream, double* ws) {
   if (n <= 0) return;
@@ -1565,16 +1609,16 @@ void launch_trsm_left_batch(const TrsmLeftDesc* descs, int n, hipStream_t stream
     order[up].push_back(i);
     if (descs[i].n <= 0 || descs[i].nrhs <= 0) continue;
     if (descs[i].invD) { inv[i] = descs[i].invD; continue; }
-    const TrsmLeftKey key{descs[i].L, up};
+    const TrsmLeftKey key = trsm_left_key(descs[i]);
     auto it = std::find_if(seen.begin(), seen.end(), [&](const auto& e) { return e.first == key; });
     if (it != seen.end()) { inv[i] = it->second; continue; }
     int nblk = (descs[i].n + 63) / 64;
     double* blk = ws + off;
     off += (size_t)nblk * 4096;
     if (up)
-      hipLaunchKernelGGL(dtrtri_diag_upper_kernel, dim3(nblk), dim3(kDiagThreads), 0, stream, descs[i].L, descs[i].ldl, descs[i].n, blk);
+      launch_trtri_diag_upper(descs[i].L, descs[i].ldl, descs[i].n, blk, stream, descs[i].unit != 0);
     else
-      hipLaunchKernelGGL(dtrtri_diag_kernel, dim3(nblk), dim3(kDiagThreads), 0, stream, descs[i].L, descs[i].ldl, descs[i].n, blk);
+      launch_trtri_diag(descs[i].L, descs[i].ldl, descs[i].n, blk, stream, descs[i].unit != 0);
     seen.emplace_back(key, blk);
     inv[i] = blk;
   }
@@ -1604,6 +1648,195 @@ void launch_trsm_left_batch(const TrsmLeftDesc* descs, int n, hipStream_t stream
       else
         hipLaunchKernelGGL(dtrsm_left_kernel<false>, dim3(total), dim3(kTrsmThreads), lds, stream, a);
     }
+  }
+}
+
+// ================================== tile GETRF without pivoting (A = L U)
+// Right-looking, blocked by 64 columns, three launches per block column j:
+//   dgetrf_diag_kernel   one workgroup: A_jj := L_jj \ U_jj in registers, then
+//                        inv(L_jj) (unit lower) and inv(U_jj) the same way
+//   dgetrf_panel_kernel  one workgroup per 64 x 64 block of the block column
+//                        below (A_ij := A_ij inv(U_jj)) and of the block row to
+//                        the right (A_jk := inv(L_jj) A_jk): one 64^3 product on
+//                        v_mfma_f64_16x16x4f64 from LDS
+//   the grouped NN GEMM  A_ik -= A_ij A_jk over the trailing part
+// No pivoting: a zero pivot is reported and the factorization goes on with
+// inf / nan. 50 KB (diagonal) and 75 KB (panel) of LDS: either fits beside one
+// resident 128 x 128 GEMM workgroup.
+constexpr int kGetrfLd = 65;   // F of the diagonal kernel: [column][row], one pad
+constexpr int kGetrfLdA = 80;  // MFMA A operand [k][row]: the two k of a 32-lane half land 32 banks apart
+constexpr int kGetrfLdB = 66;  // MFMA B operand [column][k]: 16 columns x 2 k on 32 distinct bank pairs
+
+__global__ __launch_bounds__(256) void dgetrf_diag_kernel(double* A, int lda, int j, int w, double* invL, double* invU, int* info, int info_base, int prio) {
+  __shared__ double F[64 * kGetrfLd];      // F[c][r] = (L\U)(r, c), identity-padded past w
+  __shared__ double Pn[2 * 16 * kGetrfLd];  // the two panel broadcast buffers
+  __shared__ double rcp[64];  // 1 / U(c, c)
+  __shared__ int bad_s;
+  PARSEC_WAVE_PRIO(prio);
+  double* T = A + (size_t)j * lda + j;
+  const int r = threadIdx.x & 63;
+  const int v = threadIdx.x >> 6;
+  // thread (r, v): row r, columns 16v .. 16v+15
+  double a[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = 16 * v + i;
+    a[i] = (r < w && c < w) ? T[(size_t)c * lda + r] : (r == c ? 1.0 : 0.0);
+  }
+  if (threadIdx.x == 0) bad_s = 0x7fffffff;
+  __syncthreads();
+#pragma unroll 1
+  for (int p = 0; p < 4; ++p) {
+    double* pn = Pn + (p & 1) * 16 * kGetrfLd;
+    if (v == p) {
+      // wave p factors its 64 x 16 panel: lane jc holds row jc of U
+      int bad = 0x7fffffff;
+#pragma unroll
+      for (int jj = 0; jj < 16; ++jj) {
+        const int jc = 16 * p + jj;
+        const double d = readlane_d(a[jj], jc);
+        if (d == 0.0 && bad == 0x7fffffff) bad = jc + 1;  // the padding's pivots are 1
+        const double rd = 1.0 / d;
+        if (r > jc) a[jj] *= rd;
+        const double lv = r > jc ? a[jj] : 0.0;
+#pragma unroll
+        for (int i = jj + 1; i < 16; ++i) a[i] = __builtin_fma(-lv, readlane_d(a[i], jc), a[i]);
+        if (r == jc) rcp[jc] = rd;
+      }
+      if (r == 0 && bad != 0x7fffffff) atomicMin(&bad_s, bad);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) pn[i * kGetrfLd + r] = a[i];
+    }
+    __syncthreads();
+    if (v > p) {
+      // the columns to the right: row 16p+s of U is final once the rows above it
+      // were applied; every row below takes its multiple (solve and update in one)
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {
+        const int js = 16 * p + s;
+        const double l = r > js ? pn[s * kGetrfLd + r] : 0.0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = __builtin_fma(-l, readlane_d(a[i], js), a[i]);
+      }
+    }
+  }
+  if (threadIdx.x == 0 && bad_s != 0x7fffffff && info) {
+    const int val = info_base + j + bad_s;
+    const int old = atomicCAS(info, 0, val);
+    if (old != 0 && val < old) atomicMin(info, val);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = 16 * v + i;
+    if (r < w && c < w) T[(size_t)c * lda + r] = a[i];
+    F[c * kGetrfLd + r] = a[i];
+  }
+  __syncthreads();
+  // The inverses by the same elimination on the identity, again with a row per
+  // lane and 16 columns per wave: X = inv(L) from L X = I, and Y = inv(U)^T from
+  // U^T Y = I (U^T is lower, with U's diagonal). Row js of either is final when
+  // step js starts; the rows below take their multiple of it. Columns 16v.. of a
+  // row js < 16v are still zero, so wave v starts at js = 16v.
+  double x[16], y[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) x[i] = y[i] = (r == 16 * v + i) ? 1.0 : 0.0;
+#pragma unroll 1
+  for (int js = 16 * v; js < 64; ++js) {
+    const double l = r > js ? F[js * kGetrfLd + r] : 0.0;  // L(r, js)
+    const double u = r > js ? F[r * kGetrfLd + js] : 0.0;  // U(js, r) = U^T(r, js)
+    const double rd = rcp[js];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      x[i] = __builtin_fma(-l, readlane_d(x[i], js), x[i]);
+      const double yj = readlane_d(y[i], js) * rd;
+      y[i] = r == js ? yj : __builtin_fma(-u, yj, y[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = 16 * v + i;
+    if (invL) invL[(size_t)c * 64 + r] = x[i];  // inv(L)(r, c)
+    if (invU) invU[(size_t)r * 64 + c] = y[i];  // inv(U)(c, r) = Y(r, c)
+  }
+}
+
+// blockIdx.x < nrb: block i of the column panel, A_ij := A_ij inv(U_jj);
+// else block k of the row panel, A_jk := inv(L_jj) A_jk. The diagonal block is a
+// full 64 x 64 one (there is no panel after a ragged one).
+__global__ __launch_bounds__(256) void dgetrf_panel_kernel(double* A, int lda, int n, int j, const double* __restrict__ invL, const double* __restrict__ invU, int nrb, int prio) {
+  __shared__ double As[64 * kGetrfLdA];  // As[k][row]: the left factor of the product
+  __shared__ double Bs[64 * kGetrfLdB];  // Bs[column][k]: the right factor
+  PARSEC_WAVE_PRIO(prio);
+  const bool below = (int)blockIdx.x < nrb;
+  const int o = j + 64 + 64 * (below ? (int)blockIdx.x : (int)blockIdx.x - nrb);
+  const int wb = min(64, n - o);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int fr = lane & 15, fk = lane >> 4;
+  // the block of A: rows r0.., columns c0.., mr x nc valid
+  const int r0 = below ? o : j, c0 = below ? j : o;
+  const int mr = below ? wb : 64, nc = below ? 64 : wb;
+  double* __restrict__ Ab = A + (size_t)c0 * lda + r0;
+  for (int idx = tid; idx < 4096; idx += 256) {
+    const int lo = idx & 63, hi = idx >> 6;
+    if (below) {
+      As[hi * kGetrfLdA + lo] = lo < mr ? Ab[(size_t)hi * lda + lo] : 0.0;  // A_ij(row lo, k hi)
+      Bs[hi * kGetrfLdB + lo] = invU[hi * 64 + lo];                         // inv(U)(k lo, column hi)
+    } else {
+      As[hi * kGetrfLdA + lo] = invL[hi * 64 + lo];                         // inv(L)(row lo, k hi)
+      Bs[hi * kGetrfLdB + lo] = hi < nc ? Ab[(size_t)hi * lda + lo] : 0.0;  // A_jk(k lo, column hi)
+    }
+  }
+  __syncthreads();
+  // wave wv: rows 16wv .. 16wv+15 of the product, four 16-column accumulators
+  double4_t acc[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) acc[u] = (double4_t){0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (int kk = 0; kk < 64; kk += 4) {
+    const double av = As[(kk + fk) * kGetrfLdA + 16 * wv + fr];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Bs[(16 * u + fr) * kGetrfLdB + kk + fk], acc[u], 0, 0, 0);
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int c = 16 * u + fr;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int rr = 16 * wv + fk + 4 * q;
+      if (rr < mr && c < nc) Ab[(size_t)c * lda + rr] = acc[u][q];
+    }
+  }
+}
+
+size_t getrf_workspace_bytes(const GetrfDesc& g) {
+  const size_t nblk = (size_t)((g.n + 63) / 64);
+  return ((g.invL_out ? 0 : nblk) + (g.invU_out ? 0 : nblk)) * 4096 * sizeof(double);
+}
+
+void launch_getrf_nopiv(const GetrfDesc& g, hipStream_t stream, double* ws) {
+  if (g.n <= 0) return;
+  if (g.n > kTrsmMaxCols) fatal("dgetrf tile kernel: n=%d exceeds the tile limit %d", g.n, kTrsmMaxCols);
+  if (g.lda < g.n) fatal("dgetrf tile kernel: lda=%d < n=%d", g.lda, g.n);
+  const int nblk = (g.n + 63) / 64;
+  double* il = g.invL_out ? g.invL_out : ws;
+  double* iu = g.invU_out ? g.invU_out : ws + (g.invL_out ? 0 : (size_t)nblk * 4096);
+  for (int j = 0; j < g.n; j += 64) {
+    const int jb = std::min(64, g.n - j);
+    double* bl = il + (size_t)(j / 64) * 4096;
+    double* bu = iu + (size_t)(j / 64) * 4096;
+    hipLaunchKernelGGL(dgetrf_diag_kernel, dim3(1), dim3(256), 0, stream, g.A, g.lda, j, jb, bl, bu, g.info, g.info_base, t_launch_prio);
+    const int rest = g.n - j - jb;
+    if (rest <= 0) break;
+    const int nrb = (rest + 63) / 64;
+    hipLaunchKernelGGL(dgetrf_panel_kernel, dim3(2 * nrb), dim3(256), 0, stream, g.A, g.lda, g.n, j, (const double*)bl, (const double*)bu, nrb, t_launch_prio);
+    GemmDesc e{};
+    e.A = g.A + (size_t)j * g.lda + j + jb;
+    e.B = g.A + (size_t)(j + jb) * g.lda + j;
+    e.C = g.A + (size_t)(j + jb) * g.lda + j + jb;
+    e.m = rest; e.n = rest; e.k = jb;
+    e.lda = e.ldb = e.ldc = g.lda;
+    e.alpha = -1.0; e.beta = 1.0;
+    launch_gemm_batch(&e, 1, stream);
   }
 }
 
@@ -3097,6 +3330,7 @@ size_t qr_apply_workspace_bytes(const QrApplyDesc* descs, int n);
 size_t kernel_batch_workspace_bytes(const KernelBatch& b) {
   size_t w = 0;
   for (auto& p : b.potrf) w = std::max(w, kern::potrf_steps_eligible(p) ? kern::potrf_steps_workspace_bytes(p) : kern::potrf_workspace_bytes(p));
+  for (auto& g : b.getrf) w = std::max(w, kern::getrf_workspace_bytes(g));
   if (!b.trsm_w.empty()) w = std::max(w, kern::trsm_w_workspace_bytes(b.trsm_w.data(), (int)b.trsm_w.size()));
   if (!b.qr_panel.empty()) w = std::max(w, kern::qr_panel_workspace_bytes(b.qr_panel.data(), (int)b.qr_panel.size()));
   w = std::max(w, kern::trsm_workspace_bytes(b.trsm.data(), (int)b.trsm.size()));
@@ -3128,6 +3362,7 @@ void launch_kernel_batch(KernelBatch& b, hipStream_t stream, int device_ordinal,
     if (kern::potrf_steps_eligible(p)) kern::launch_potrf_steps(p, stream, static_cast<double*>(ws));
     else kern::launch_potrf(p, stream, static_cast<double*>(ws));
   }
+  for (auto& g : b.getrf) kern::launch_getrf_nopiv(g, stream, static_cast<double*>(ws));
   if (!b.qr_panel.empty()) kern::launch_qr_panel_blocked(b.qr_panel.data(), (int)b.qr_panel.size(), stream, static_cast<double*>(ws));
   if (!b.trsm.empty()) kern::launch_trsm_batch(b.trsm.data(), (int)b.trsm.size(), stream, static_cast<double*>(ws));
   if (!b.trsm_w.empty()) kern::launch_trsm_w_batch(b.trsm_w.data(), (int)b.trsm_w.size(), stream, static_cast<double*>(ws));
@@ -3319,6 +3554,13 @@ int parsec_amd_dpotrf_tile(double* A, int n, int lda, int* info, void* stream) {
   }
   void* ws = test_ws(4096 * sizeof(double));
   parsec::kern::launch_potrf(p, (hipStream_t)stream, static_cast<double*>(ws));
+  return (int)hipGetLastError();
+}
+// Tile LU without pivoting; invL / invU (optional) receive the diagonal-block inverses
+int parsec_amd_dgetrf_nopiv_tile(double* A, int n, int lda, int* info, double* invL, double* invU, void* stream) {
+  parsec::GetrfDesc g{A, n, lda, info, invL, invU};
+  void* ws = test_ws(parsec::kern::getrf_workspace_bytes(g) + 64);
+  parsec::kern::launch_getrf_nopiv(g, (hipStream_t)stream, static_cast<double*>(ws));
   return (int)hipGetLastError();
 }
 // Tile Cholesky that also writes W = L^-1 (ld ldw)

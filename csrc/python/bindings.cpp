@@ -31,6 +31,7 @@ extern "C" int parsec_amd_potrf_steps(int on);
 extern "C" int parsec_amd_potrf_stamps(long long* out);
 extern "C" int parsec_amd_dtrsm_batch(const TrsmDesc* descs, int n, void* stream);
 extern "C" int parsec_amd_dtrsm_left_batch(const TrsmLeftDesc* descs, int n, void* stream);
+extern "C" int parsec_amd_dgetrf_nopiv_tile(double* A, int n, int lda, int* info, double* invL, double* invU, void* stream);
 extern "C" int parsec_amd_dpotrf_tile(double* A, int n, int lda, int* info, void* stream);
 extern "C" int parsec_amd_trsm_w_batch(const parsec::TrsmGemmDesc* d, int n, void* stream);
 extern "C" int parsec_amd_dpotrf_tile_w(double* A, int n, int lda, int* info, double* W, int ldw, void* stream, int pack);
@@ -532,6 +533,35 @@ PYBIND11_MODULE(_C, m) {
         return py::make_tuple(py::cast(tp, py::return_value_policy::reference), (uintptr_t)info);
       }, py::arg("uplo"), py::arg("A"), py::arg("B"),
       "Cholesky factorization then solve (lower, one rank); returns (taskpool, info address) or None. When info != 0 the solve does not run and B is untouched");
+  m.def("dgetrf_nopiv_new", [](TiledMatrix* A) -> py::object {
+        auto* info = new int(0);
+        auto* tp = algos::dgetrf_nopiv_new(A, info);
+        if (!tp) {
+          delete info;
+          return py::none();
+        }
+        auto prev = tp->destructor_hook;
+        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
+        return py::make_tuple(py::cast(tp, py::return_value_policy::take_ownership), (uintptr_t)info);
+      }, py::arg("A"),
+      "tiled LU WITHOUT pivoting (square A, square tiles) from the ptgpp-compiled dgetrf_nopiv.jdf: A := L\\U, L unit lower; returns (taskpool, info address) or "
+      "None. info is the 1-based index of the first pivot that is exactly zero; the matrix must not need pivoting");
+  m.def("dgetrs_nopiv_new", [](int trans, TiledMatrix* A, TiledMatrix* B) { return algos::dgetrs_nopiv_new(trans, A, B); }, py::arg("trans"), py::arg("A"),
+        py::arg("B"), py::return_value_policy::reference,
+        "solve op(A) X = B with the factor of dgetrf_nopiv_new in A (MATRIX_NOTRANS or MATRIX_TRANS); B.mb must equal A.nb; None on invalid arguments. Release "
+        "with taskpool_free");
+  m.def("dgesv_nopiv_new", [](TiledMatrix* A, TiledMatrix* B) -> py::object {
+        auto* info = new int(0);
+        Taskpool* tp = algos::dgesv_nopiv_new(A, B, info);
+        if (!tp) {
+          delete info;
+          return py::none();
+        }
+        auto prev = tp->destructor_hook;
+        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
+        return py::make_tuple(py::cast(tp, py::return_value_policy::reference), (uintptr_t)info);
+      }, py::arg("A"), py::arg("B"),
+      "LU without pivoting then solve (one rank); returns (taskpool, info address) or None. When info != 0 the solve does not run and B is untouched");
   m.def("dormqr_new", [](int side, int trans, TiledMatrix* A, TiledMatrix* T, TiledMatrix* B) { return (Taskpool*)algos::dormqr_new(side, trans, A, T, B); },
         py::arg("side"), py::arg("trans"), py::arg("A"), py::arg("T"), py::arg("B"), py::return_value_policy::reference,
         "B := op(Q) B with the Q of dgeqrf_jdf_new / dgeqrf_new (not dgeqrf_hqr_new) in A and T: MATRIX_LEFT, MATRIX_TRANS or MATRIX_NOTRANS; B.mb must equal "
@@ -759,20 +789,29 @@ PYBIND11_MODULE(_C, m) {
     t.L = (const double*)L; t.B = (double*)B; t.m = mm; t.n = nn; t.ldl = ldl; t.ldb = ldb; t.trans = 1;
     return parsec_amd_dtrsm_batch(&t, 1, (void*)stream);
   });
-  m.def("kernel_dtrsm_left", [](uintptr_t L, uintptr_t B, int n, int nrhs, int ldl, int ldb, double alpha, int trans, uintptr_t stream, int upper) {
-    TrsmLeftDesc t{(const double*)L, (double*)B, n, nrhs, ldl, ldb, alpha, (uint8_t)(trans ? 1 : 0), (uint8_t)(upper ? 1 : 0), nullptr};
+  m.def("kernel_dtrsm_left", [](uintptr_t L, uintptr_t B, int n, int nrhs, int ldl, int ldb, double alpha, int trans, uintptr_t stream, int upper, int unit, int right) {
+    TrsmLeftDesc t{(const double*)L, (double*)B, n, nrhs, ldl, ldb, alpha, (uint8_t)(trans ? 1 : 0), (uint8_t)(upper ? 1 : 0), (uint8_t)(unit ? 1 : 0),
+                   (uint8_t)(right ? 1 : 0), nullptr};
     return parsec_amd_dtrsm_left_batch(&t, 1, (void*)stream);
   }, py::arg("L"), py::arg("B"), py::arg("n"), py::arg("nrhs"), py::arg("ldl"), py::arg("ldb"), py::arg("alpha") = 1.0, py::arg("trans") = 0, py::arg("stream") = 0,
-     py::arg("upper") = 0,
-     "B := alpha op(L)^-1 B on the GPU: L n x n lower, or upper with upper=1 (column-major, only that triangle is read), B n x nrhs; trans 1 solves with L^T");
-  // grouped launch: tuples (L, B, n, nrhs, ldl, ldb, alpha, trans[, upper])
+     py::arg("upper") = 0, py::arg("unit") = 0, py::arg("right") = 0,
+     "B := alpha op(L)^-1 B on the GPU: L n x n lower, or upper with upper=1 (column-major, only that triangle is read), B n x nrhs; trans 1 solves with L^T; "
+     "unit=1 takes L's diagonal as 1 without reading it; right=1 solves X op(L) = alpha B with B nrhs x n (nrhs rows)");
+  m.def("kernel_dgetrf_nopiv", [](uintptr_t A, int n, int lda, uintptr_t info, uintptr_t invL, uintptr_t invU, uintptr_t stream) {
+    return parsec_amd_dgetrf_nopiv_tile((double*)A, n, lda, (int*)info, (double*)invL, (double*)invU, (void*)stream);
+  }, py::arg("A"), py::arg("n"), py::arg("lda"), py::arg("info") = 0, py::arg("invL") = 0, py::arg("invU") = 0, py::arg("stream") = 0,
+     "tile LU without pivoting on the GPU: the n x n column-major tile A := L\\U (L unit lower); info (device int, optional) receives the 1-based index of the "
+     "first zero pivot; invL / invU (optional, ceil(n/64) x 4096 doubles) the inverses of the 64 x 64 diagonal blocks of L and U");
+  // grouped launch: tuples (L, B, n, nrhs, ldl, ldb, alpha, trans[, upper[, unit[, right]]])
   m.def("kernel_dtrsm_left_batch", [](const std::vector<py::tuple>& ds, uintptr_t stream) {
     std::vector<TrsmLeftDesc> v;
     for (const auto& d : ds) {
-      if (d.size() != 8 && d.size() != 9) throw std::invalid_argument("kernel_dtrsm_left_batch: tuples of (L, B, n, nrhs, ldl, ldb, alpha, trans[, upper])");
+      if (d.size() < 8 || d.size() > 11)
+        throw std::invalid_argument("kernel_dtrsm_left_batch: tuples of (L, B, n, nrhs, ldl, ldb, alpha, trans[, upper[, unit[, right]]])");
       v.push_back(TrsmLeftDesc{(const double*)d[0].cast<uintptr_t>(), (double*)d[1].cast<uintptr_t>(), d[2].cast<int>(), d[3].cast<int>(), d[4].cast<int>(),
                                d[5].cast<int>(), d[6].cast<double>(), (uint8_t)(d[7].cast<int>() ? 1 : 0),
-                               (uint8_t)(d.size() == 9 && d[8].cast<int>() ? 1 : 0), nullptr});
+                               (uint8_t)(d.size() >= 9 && d[8].cast<int>() ? 1 : 0), (uint8_t)(d.size() >= 10 && d[9].cast<int>() ? 1 : 0),
+                               (uint8_t)(d.size() >= 11 && d[10].cast<int>() ? 1 : 0), nullptr});
     }
     return parsec_amd_dtrsm_left_batch(v.data(), (int)v.size(), (void*)stream);
   });

@@ -693,6 +693,21 @@ parsec_taskpool_t* parsec_dormqr_New(parsec_matrix_side_t side, parsec_matrix_tr
                                      parsec_tiled_matrix_t* B);
 parsec_taskpool_t* parsec_dgeqrs_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* T, parsec_tiled_matrix_t* B);
 parsec_taskpool_t* parsec_dgels_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* T, parsec_tiled_matrix_t* B);
+/* LU WITHOUT pivoting of a square double matrix with square tiles (a ragged
+ * last tile is allowed; the ptgpp-compiled dgetrf_nopiv.jdf, DPLASMA's
+ * dplasma_dgetrf_nopiv_New role): A := L\U, L unit lower. The matrix must not
+ * need pivoting (diagonally dominant, or preconditioned): *info holds the
+ * 1-based global index of the first pivot that is exactly zero once the
+ * taskpool completed (0: none); a merely small pivot is not reported.
+ * parsec_dgetrs_nopiv_New: op(A) X = B with that factor, PARSEC_MATRIX_NOTRANS
+ * or PARSEC_MATRIX_TRANS; B is N x NRHS with B->mb == A->nb, on any process
+ * grid. parsec_dgesv_nopiv_New: factor then solve in one taskpool; with
+ * *info != 0 the solve does not run and B is untouched; info is required; one
+ * rank only. All return NULL (after a warning) for any other request or shape;
+ * release the two composed ones with parsec_taskpool_free. */
+parsec_taskpool_t* parsec_dgetrf_nopiv_New(parsec_tiled_matrix_t* A, int* info);
+parsec_taskpool_t* parsec_dgetrs_nopiv_New(parsec_matrix_trans_t trans, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B);
+parsec_taskpool_t* parsec_dgesv_nopiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info);
 int parsec_apply(parsec_context_t* parsec, parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_unary_op_t operation, void* op_args);
 /* op(es, src_tile, dest_tile, op_data, m, n) for every tile of dest */
 parsec_taskpool_t* parsec_map_operator_New(const parsec_tiled_matrix_t* src, parsec_tiled_matrix_t* dest, parsec_operator_t op, void* op_data);

@@ -56,6 +56,7 @@ CORE_SOURCES = [
     "csrc/algos/dgeqrf_jdf.cpp",
     "csrc/algos/dtrsm_jdf.cpp",
     "csrc/algos/dgels_jdf.cpp",
+    "csrc/algos/dgetrf_jdf.cpp",
     "csrc/algos/redistribute_ptg.cpp",
 ]
 HIP_SOURCES = [
@@ -72,6 +73,7 @@ JDF_SOURCES = [
     "csrc/algos/jdf/dgeqrf.jdf",
     "csrc/algos/jdf/dtrsm_LL.jdf",
     "csrc/algos/jdf/dtrsm_LU.jdf",
+    "csrc/algos/jdf/dgetrf_nopiv.jdf",
     "csrc/algos/jdf/dormqr.jdf",
     "csrc/algos/jdf/redistribute.jdf",
     "csrc/algos/jdf/redistribute_reshuffle.jdf",
@@ -79,7 +81,7 @@ JDF_SOURCES = [
 ]
 # runtime sources that include generated JDF headers
 JDF_USERS = ["csrc/algos/dpotrf_jdf.cpp", "csrc/algos/dgeqrf_jdf.cpp", "csrc/algos/dtrsm_jdf.cpp", "csrc/algos/dgels_jdf.cpp",
-             "csrc/algos/redistribute_ptg.cpp"]
+             "csrc/algos/dgetrf_jdf.cpp", "csrc/algos/redistribute_ptg.cpp"]
 FORTRAN_SOURCES = ["csrc/fortran/parsecf.F90", "csrc/fortran/parsec_profilef.F90"]
 FLANG = os.path.join(ROCM, "lib", "llvm", "bin", "flang")
 TEST_SOURCES = ["tests/native/test_containers.cpp", "tests/native/test_futures.cpp", "tests/native/test_fetch_queue.cpp"]
@@ -275,7 +277,8 @@ def generate_sanitized(kind):
     # C API programs run instrumented: the DTD program and the distributed PTG
     # Cholesky (ptgpp-compiled dpotrf_L.jdf, CPU bodies on 1..4 ranks); the
     # factor-and-solve program (dtrsm_LL.jdf) is built beside them
-    for capi in ("tests/capi/dtd_capi.c", "tests/capi/dpotrf_capi.c", "tests/capi/dpotrs_capi.c", "tests/capi/dgels_capi.c"):
+    for capi in ("tests/capi/dtd_capi.c", "tests/capi/dpotrf_capi.c", "tests/capi/dpotrs_capi.c", "tests/capi/dgels_capi.c",
+                 "tests/capi/dgetrf_capi.c"):
         if not os.path.exists(os.path.join(ROOT, capi)):
             continue
         name = os.path.splitext(os.path.basename(capi))[0]
