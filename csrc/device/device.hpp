@@ -234,6 +234,36 @@ int trsm_inplace(int set);
 void trsm_estimate_forget(const void* p);
 double trsm_estimate_lookup(const void* p);
 std::vector<uintptr_t> trsm_estimate_known();
+// What the host decided for one grouped-DGEMM launch (launch_gemm_shape): the
+// tile shape, the operand mode, the tile / workgroup counts and the kernel
+// variant that went out.
+struct GemmLaunchRecord {
+  int bm, bn;
+  int descs;        // descriptors of the launch
+  int total_tiles;  // tiles of all descriptors
+  int main_tiles;   // tiles run whole; the other total_tiles - main_tiles are split ksplit ways along K
+  int ksplit;
+  int grid;         // workgroups
+  int pad_bytes;    // extra dynamic LDS (one bulk workgroup per CU)
+  uint8_t transA, transB;
+  uint8_t full;     // unchecked loads
+  uint8_t epilogue; // 0 plain (C preload when |alpha| = 1), 1 atomic, 2 late C
+  uint8_t rotated, direct_lds, persistent;
+  uint8_t ordered;  // in-place descriptors: tiles in dispatch order
+};
+constexpr int kGemmLaunchLogSize = 64;
+// Per-thread record of the last kGemmLaunchLogSize grouped-DGEMM launches,
+// written only while switched on: on 1 / 0, < 0 queries; returns the previous setting.
+int gemm_launch_log(int on);
+// Copies the calling thread's records, oldest first, to out (room for
+// kGemmLaunchLogSize) and returns their number; reset empties the record.
+int gemm_launch_log_read(GemmLaunchRecord* out, bool reset);
+// Round-filling launch chunks on (1) / off (0: fixed launches of 40 descriptors), < 0 queries; returns the previous setting.
+int gemm_chunk_fill(int on);
+// The launch chunks launch_gemm_batch cuts for count descriptors of one operand
+// mode with C of m[i] x n[i], on `slots` resident 128 x 128 workgroups: their
+// lengths go to out (room for count), their number is returned. Host code only.
+int gemm_chunk_plan(const int* m, const int* n, int count, int slots, int* out);
 }  // namespace kern
 
 // Householder QR of a tile (GEQRT: A2 == nullptr) or of a triangle on top of a

@@ -211,7 +211,10 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
   if (d.b_upper) kfull = min(kfull, n0 + BN);  // op(B) upper triangular: column block n0 reads k < n0 + BN
   const int kchunk = nsplit > 1 ? (((kfull + nsplit - 1) / nsplit + BK - 1) / BK) * BK : kfull;
   const int kbeg = ks * kchunk;
-  if (kbeg >= kfull) return;
+  // an empty K chunk of a split tile adds nothing. K = 0 itself (ks == 0: the
+  // host keeps it out of the FULL launches, whose prologue loads k-tile 0
+  // unconditionally) runs the epilogue with zero accumulators: C := beta C
+  if (kbeg >= kfull && (FULL || ks > 0)) return;
   const int K = min(kfull, kbeg + kchunk) - kbeg;
   crit_claim(args.claim);
   const double* __restrict__ A = d.A + (TRANSA ? (size_t)kbeg : (size_t)kbeg * lda);
@@ -1213,6 +1216,11 @@ static int g_gemm_chunk_fill = -1;   // PARSEC_GEMM_CHUNK_FILL=0: fixed 40-descr
 // launches are padded to one workgroup per CU (t_launch_pad)
 static inline int gemm_slots() { return t_launch_pad ? std::max(1, g_gemm_slots / 2) : g_gemm_slots; }
 
+// launch record of this thread (gemm_launch_log): a ring of the last launches
+static thread_local bool t_gemm_log_on = false;
+static thread_local GemmLaunchRecord t_gemm_log[kGemmLaunchLogSize];
+static thread_local unsigned t_gemm_log_count = 0;  // records written since the last reset
+
 template <int BM, int BN, int BK, int WM, int WN, int NBUF, int OCC = WM * WN / 2, int PF = 1>
 static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hipStream_t stream) {
   a.prio = t_launch_prio;
@@ -1223,7 +1231,7 @@ static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hi
   bool full = g_gemm_full != 0;
   for (int i = 0; i < n; ++i) {
     const GemmDesc& g = descs[i];
-    full = full && g.m % BM == 0 && g.n % BN == 0 && g.k % BK == 0 && (g.lda | g.ldb) % 2 == 0 &&
+    full = full && g.m % BM == 0 && g.n % BN == 0 && g.k > 0 && g.k % BK == 0 && (g.lda | g.ldb) % 2 == 0 &&
            ((uintptr_t)g.A | (uintptr_t)g.B) % 16 == 0;
     a.d[i] = g;
     a.tile_start[i] = total;
@@ -1298,6 +1306,20 @@ static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hi
     grid_size = slots;
   }
   const dim3 grid(grid_size), block(WM * WN * 64);
+  // the kernel that goes out, noted beside its launch
+  auto note = [&](bool k_full, int k_epi, bool k_rot, bool k_dl, bool k_persist) {
+    if (!t_gemm_log_on) return;
+    GemmLaunchRecord& r = t_gemm_log[t_gemm_log_count++ % kGemmLaunchLogSize];
+    r.bm = BM; r.bn = BN;
+    r.descs = n;
+    r.total_tiles = total; r.main_tiles = a.main_tiles; r.ksplit = a.ksplit;
+    r.grid = grid_size;
+    r.pad_bytes = (int)pad;
+    r.transA = (mode & 2) != 0; r.transB = (mode & 1) != 0;
+    r.full = k_full; r.epilogue = (uint8_t)k_epi;
+    r.rotated = k_rot; r.direct_lds = k_dl; r.persistent = k_persist;
+    r.ordered = ordered;
+  };
   if (pad) {
     static bool said = false;
     if (!said && getenv("PARSEC_GEMM_PAD_DEBUG")) {
@@ -1309,14 +1331,17 @@ static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hi
   do {                                                                                                                                      \
     if constexpr (!(TA) && (TB) && BM == 128 && BN == 128 && (NBUF == 2 || NBUF == 3) && PF == 1)                                          \
       if (dl && full && !persist) {                                                                                                          \
+        note(true, E, false, true, false);                                                                                                   \
         hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E, true>), grid, block, pad, stream, a);     \
         break;                                                                                                                               \
       }                                                                                                                                      \
     if constexpr (NBUF == 2 && PF == 1)                                                                                                      \
       if (rot && full && !persist) {                                                                                                         \
+        note(true, E, true, false, false);                                                                                                   \
         hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E, false, false, 1>), grid, block, pad, stream, a); \
         break;                                                                                                                               \
       }                                                                                                                                      \
+    note(full, full ? E : 0, false, false, persist);                                                                                         \
     if (persist) hipLaunchKernelGGL((dgemm_persist_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E>), grid, block, pad, stream, a);  \
     else if (full) hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E>), grid, block, pad, stream, a);  \
     else hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, false, NBUF, OCC, PF, 0>), grid, block, pad, stream, a);          \
@@ -1327,9 +1352,11 @@ static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hi
       if (late && !persist) {                                                                                       \
         if constexpr (NBUF == 2 && PF == 1)                                                                         \
           if (rot) {                                                                                                \
+            note(true, 2, true, false, false);                                                                      \
             hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, 2, PF, 2, false, false, 1>), grid, block, pad, stream, a); \
             break;                                                                                                  \
           }                                                                                                         \
+        note(true, 2, false, false, false);                                                                         \
         hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, 2, PF, 2>), grid, block, pad, stream, a); \
         break;                                                                                                      \
       }                                                                                                             \
@@ -1340,6 +1367,7 @@ static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hi
   if (ordered) {
     // in-place panel solve (launch_trsm_w_batch): NT descriptors, plain epilogue
     if (mode != 1 || epi || late) fatal("in-place GEMM launch: NT descriptors with the plain epilogue only");
+    note(full, 0, false, false, false);
     if (full) hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, false, true, true, NBUF, OCC, PF, 0, false, true>), grid, block, pad, stream, a);
     else hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, false, true, false, NBUF, OCC, PF, 0, false, true>), grid, block, pad, stream, a);
     return;
@@ -1392,6 +1420,27 @@ int gemm_mainloop(int mode) {
   const int prev = g_gemm_mainloop;
   if (mode >= 0) g_gemm_mainloop = mode == 0 ? 0 : 1;
   return prev;
+}
+
+// Round-filling launch chunks on (1) / off (0), < 0 queries; returns the previous setting.
+int gemm_chunk_fill(int on) {
+  gemm_policy_init();
+  const int prev = g_gemm_chunk_fill;
+  if (on >= 0) g_gemm_chunk_fill = on != 0;
+  return prev;
+}
+
+int gemm_launch_log(int on) {
+  const int prev = t_gemm_log_on;
+  if (on >= 0) t_gemm_log_on = on != 0;
+  return prev;
+}
+
+int gemm_launch_log_read(GemmLaunchRecord* out, bool reset) {
+  const unsigned have = std::min<unsigned>(t_gemm_log_count, kGemmLaunchLogSize);
+  for (unsigned i = 0; i < have; ++i) out[i] = t_gemm_log[(t_gemm_log_count - have + i) % kGemmLaunchLogSize];
+  if (reset) t_gemm_log_count = 0;
+  return (int)have;
 }
 
 // Tile-size policy of the grouped GEMM (0 = auto, 64, 128); returns the previous one.
@@ -1450,14 +1499,14 @@ static void launch_gemm_chunk(const GemmDesc* descs, int n, hipStream_t stream) 
 // that fills whole rounds of resident 128x128 workgroups best. 40 tiles of
 // 512^2 are 640 128-tiles = 1.25 rounds of 512 slots (62 % of the second round
 // idle); 32 of them are exactly one round.
-static int gemm_chunk_size(const GemmDesc* d, int n) {
+template <class Tiles128>  // tiles128(i): 128 x 128 tiles of descriptor i
+static int gemm_chunk_cut(Tiles128 tiles128, int n, int slots, bool fill_rounds) {
   const int cap = std::min(n, kMaxGemmBatch);
-  if (g_gemm_chunk_fill == 0) return cap;
+  if (!fill_rounds) return cap;
   int best = cap, tiles = 0;
   double best_fill = -1.0;
   for (int c = 1; c <= cap; ++c) {
-    tiles += ((d[c - 1].m + 127) / 128) * ((d[c - 1].n + 127) / 128);
-    const int slots = gemm_slots();
+    tiles += tiles128(c - 1);
     if (tiles < slots) continue;
     const int rounds = (tiles + slots - 1) / slots;
     const double fill = (double)tiles / ((double)rounds * slots);
@@ -1465,13 +1514,44 @@ static int gemm_chunk_size(const GemmDesc* d, int n) {
   }
   return best_fill >= 0.0 ? best : cap;
 }
+static int gemm_chunk_size(const GemmDesc* d, int n) {
+  return gemm_chunk_cut([d](int i) { return ((d[i].m + 127) / 128) * ((d[i].n + 127) / 128); }, n, gemm_slots(), g_gemm_chunk_fill != 0);
+}
+int gemm_chunk_plan(const int* m, const int* n, int count, int slots, int* out) {
+  // no device needed: before the policies are read, the setting is the environment's
+  int fill = g_gemm_chunk_fill;
+  if (fill < 0) fill = getenv("PARSEC_GEMM_CHUNK_FILL") ? atoi(getenv("PARSEC_GEMM_CHUNK_FILL")) : 1;
+  int cuts = 0;
+  for (int s = 0; s < count;) {
+    const int c = gemm_chunk_cut([&](int i) { return ((m[s + i] + 127) / 128) * ((n[s + i] + 127) / 128); }, count - s, std::max(1, slots), fill != 0);
+    out[cuts++] = c;
+    s += c;
+  }
+  return cuts;
+}
 
 // Group descriptors by (transA, transB): one grouped launch per combination
 // (the vendor library is an A/B reference only: scripts/kbench_gemm_vs_vendor.py).
+// A descriptor with alpha == 0 or k <= 0 references neither A nor B (BLAS): it
+// goes out as K = 0 in a launch of its own kind, C := beta C from the
+// bounds-checked kernel's epilogue, so NaN / Inf in the operands stay out of C
+// and the k loops carry no test for it. (Gated and in-place descriptors are
+// protocols of the panel solve and stay where they are.)
 void launch_gemm_batch(const GemmDesc* descs, int n, hipStream_t stream) {
   gemm_policy_init();
-  std::vector<GemmDesc> g[4];
-  for (int i = 0; i < n; ++i) g[(descs[i].transA ? 2 : 0) | (descs[i].transB ? 1 : 0)].push_back(descs[i]);
+  std::vector<GemmDesc> g[5];
+  for (int i = 0; i < n; ++i) {
+    const GemmDesc& d = descs[i];
+    if ((d.alpha == 0.0 || d.k <= 0) && !d.gate && !d.inplace) {
+      GemmDesc z = d;
+      z.k = 0;
+      z.transA = z.transB = 0;
+      z.a_lower = z.b_upper = 0;
+      g[4].push_back(z);
+    } else {
+      g[(d.transA ? 2 : 0) | (d.transB ? 1 : 0)].push_back(d);
+    }
+  }
   for (auto& v : g) {
     for (size_t s = 0; s < v.size();) {
       const int c = gemm_chunk_size(v.data() + s, (int)(v.size() - s));

@@ -24,6 +24,8 @@ namespace py = pybind11;
 using namespace parsec;
 
 extern "C" int parsec_amd_dgemm_batch(const GemmDesc* descs, int n, void* stream);
+extern "C" int parsec_amd_dgemm(char transa, char transb, int m, int n, int k, double alpha, const double* A, int lda, const double* B, int ldb, double beta,
+                                double* C, int ldc, void* stream);
 extern "C" int parsec_amd_gemm_tile_policy(int p);
 extern "C" int parsec_amd_gemm_splitk(int on);
 extern "C" int parsec_amd_gemm_mainloop(int mode);
@@ -766,6 +768,68 @@ PYBIND11_MODULE(_C, m) {
     }
     return parsec_amd_dgemm_batch(v.data(), (int)v.size(), (void*)stream);
   });
+  // every GemmDesc field but the gate / inplace protocols (those run through kernel_trsm_w_batch); missing keys are 0
+  m.def("kernel_dgemm_batch_ex", [](const std::vector<py::dict>& ds, uintptr_t stream) {
+    static const char* const known[] = {"A", "B", "C", "m", "n", "k", "lda", "ldb", "ldc", "alpha", "beta", "transA", "transB", "lower_only", "a_lower",
+                                        "b_upper", "Cin", "ldcin", "C2", "ldc2"};
+    std::vector<GemmDesc> v;
+    for (const auto& d : ds) {
+      for (const auto& kv : d) {
+        const std::string key = py::cast<std::string>(kv.first);
+        bool ok = false;
+        for (const char* k : known) ok = ok || key == k;
+        if (!ok) throw std::invalid_argument("kernel_dgemm_batch_ex: unknown descriptor key '" + key + "'");
+      }
+      auto ptr = [&](const char* k) { return d.contains(k) ? d[k].cast<uintptr_t>() : (uintptr_t)0; };
+      auto num = [&](const char* k) { return d.contains(k) ? d[k].cast<int>() : 0; };
+      auto real = [&](const char* k) { return d.contains(k) ? d[k].cast<double>() : 0.0; };
+      GemmDesc g{};
+      g.A = (const double*)ptr("A"); g.B = (const double*)ptr("B"); g.C = (double*)ptr("C");
+      g.m = num("m"); g.n = num("n"); g.k = num("k");
+      g.lda = num("lda"); g.ldb = num("ldb"); g.ldc = num("ldc");
+      g.alpha = real("alpha"); g.beta = real("beta");
+      g.transA = num("transA") ? 1 : 0; g.transB = num("transB") ? 1 : 0;
+      g.lower_only = num("lower_only") ? 1 : 0; g.a_lower = num("a_lower") ? 1 : 0; g.b_upper = num("b_upper") ? 1 : 0;
+      g.Cin = (const double*)ptr("Cin"); g.ldcin = num("ldcin");
+      g.C2 = (double*)ptr("C2"); g.ldc2 = num("ldc2");
+      v.push_back(g);
+    }
+    return parsec_amd_dgemm_batch(v.data(), (int)v.size(), (void*)stream);
+  }, py::arg("descs"), py::arg("stream") = 0, "grouped DGEMM from dicts keyed by the GemmDesc fields (device pointers as ints)");
+  m.def("kernel_dgemm_blas", [](const std::string& transa, const std::string& transb, int mm, int nn, int kk, double alpha, uintptr_t A, int lda, uintptr_t B, int ldb,
+                                double beta, uintptr_t C, int ldc, uintptr_t stream) {
+    if (transa.size() != 1 || transb.size() != 1) throw std::invalid_argument("kernel_dgemm_blas: transa / transb are one character each");
+    return parsec_amd_dgemm(transa[0], transb[0], mm, nn, kk, alpha, (const double*)A, lda, (const double*)B, ldb, beta, (double*)C, ldc, (void*)stream);
+  }, py::arg("transa"), py::arg("transb"), py::arg("m"), py::arg("n"), py::arg("k"), py::arg("alpha"), py::arg("A"), py::arg("lda"), py::arg("B"), py::arg("ldb"),
+     py::arg("beta"), py::arg("C"), py::arg("ldc"), py::arg("stream") = 0, "the public parsec_amd_dgemm: C = alpha op(A) op(B) + beta C, column major");
+  m.def("kernel_gemm_launch_log", [](py::object enable, bool reset) {
+    kern::GemmLaunchRecord recs[kern::kGemmLaunchLogSize];
+    const int cnt = kern::gemm_launch_log_read(recs, reset);
+    if (!enable.is_none()) kern::gemm_launch_log(enable.cast<bool>() ? 1 : 0);
+    py::list out;
+    for (int i = 0; i < cnt; ++i) {
+      const kern::GemmLaunchRecord& r = recs[i];
+      py::dict e;
+      e["BM"] = r.bm; e["BN"] = r.bn;
+      e["transA"] = (int)r.transA; e["transB"] = (int)r.transB;
+      e["descs"] = r.descs;
+      e["total_tiles"] = r.total_tiles; e["main_tiles"] = r.main_tiles; e["ksplit"] = r.ksplit;
+      e["grid"] = r.grid;
+      e["full"] = (bool)r.full; e["epilogue"] = (int)r.epilogue;
+      e["rotated"] = (bool)r.rotated; e["direct_lds"] = (bool)r.direct_lds; e["persistent"] = (bool)r.persistent; e["ordered"] = (bool)r.ordered;
+      e["pad_bytes"] = r.pad_bytes;
+      out.append(e);
+    }
+    return out;
+  }, py::arg("enable") = py::none(), py::arg("reset") = false,
+     "grouped-DGEMM launches the calling thread recorded (oldest first, the last 64): a dict per launch; reset empties the record, enable switches recording on / off");
+  m.def("kernel_gemm_chunk_fill", [](int on) { return kern::gemm_chunk_fill(on); }, "round-filling launch chunks of the grouped DGEMM: 1 on, 0 off (fixed launches of 40 descriptors), -1 query; returns the previous setting");
+  m.def("kernel_gemm_chunk_plan", [](const std::vector<std::pair<int, int>>& shapes, int slots) {
+    std::vector<int> mm, nn, out(shapes.size());
+    for (const auto& s : shapes) { mm.push_back(s.first); nn.push_back(s.second); }
+    out.resize((size_t)kern::gemm_chunk_plan(mm.data(), nn.data(), (int)shapes.size(), slots, out.data()));
+    return out;
+  }, py::arg("shapes"), py::arg("slots"), "descriptors per launch the grouped DGEMM cuts for C shapes [(m, n), ...] of one operand mode on `slots` resident 128x128 workgroups (host code only)");
   m.def("kernel_gemm_tile_policy", [](int p) { return parsec_amd_gemm_tile_policy(p); });
   m.def("kernel_gemm_splitk", [](int on) { return parsec_amd_gemm_splitk(on); }, "split-K tail of the 128x128 grouped DGEMM: 1 on, 0 off, -1 query; returns the previous setting");
   m.def("kernel_gemm_mainloop", [](int mode) { return parsec_amd_gemm_mainloop(mode); }, "k loop of the full register-staged grouped DGEMM: 0 plain, 1 rotated, -1 query; returns the previous setting");

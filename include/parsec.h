@@ -988,7 +988,10 @@ void* parsec_gpu_stream_info_get(parsec_info_id_t iid);
 
 /* ------------------------------------------------------------ tile kernels
  * The framework's MFMA DGEMM as a BLAS-style call on a HIP stream (column
- * major; trans 'N' or 'T'); returns a hipError_t (0 = success). */
+ * major; trans 'N', or 'T' / 'C' for the transpose, either case); returns a
+ * hipError_t (0 = success). As in BLAS, m == 0 or n == 0 does nothing, and
+ * k == 0 or alpha == 0 gives C := beta C without referencing A or B (beta == 0
+ * does not read C either). */
 int parsec_amd_dgemm(char transa, char transb, int m, int n, int k, double alpha, const double* A, int lda, const double* B, int ldb, double beta,
                      double* C, int ldc, void* stream);
 

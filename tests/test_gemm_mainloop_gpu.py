@@ -192,12 +192,22 @@ def test_split_k_tail(pa, dev):
     Cs = [_cm(n, n, dev, g) for _ in range(cnt)]
     refs = [C - A @ B.t() for A, B, C in zip(As, Bs, Cs)]
     descs = [(A.data_ptr(), B.data_ptr(), C.data_ptr(), n, n, n, n, n, n, -1.0, 1.0, 1, 0) for A, B, C in zip(As, Bs, Cs)]
+    # one launch of all 9 per loop (the round-filling chunks would cut 8 + 1 and never split)
     prev = pa.kernel_gemm_splitk(1)
+    prev_fill = pa.kernel_gemm_chunk_fill(0)
+    pa.kernel_gemm_launch_log(True, reset=True)
     try:
         with _policy(pa, 0):
             res = _both(pa, Cs, lambda: pa.kernel_dgemm_batch(descs, _stream()))
+        log = pa.kernel_gemm_launch_log()
     finally:
+        pa.kernel_gemm_launch_log(False, reset=True)
+        pa.kernel_gemm_chunk_fill(prev_fill)
         pa.kernel_gemm_splitk(prev)
+    assert len(log) == 2, log  # the plain loop, then the rotated one
+    for rec, rotated in zip(log, (False, True)):
+        assert (rec["BM"], rec["descs"], rec["ksplit"], rec["rotated"], rec["full"]) == (128, cnt, 4, rotated, True), rec
+        assert rec["total_tiles"] == 576 and rec["main_tiles"] < 576, rec
     for r in res:
         for C, ref in zip(r, refs):
             err = ((C - ref).abs().max() / ref.abs().max()).item()

@@ -94,12 +94,21 @@ def test_dgemm_batch_split_k_tail(pa, syrk):
     C0 = [C.clone() for C in Cs]
     refs = [C - A @ B.t() for A, B, C in zip(As, Bs, Cs)]
     descs = [(A.data_ptr(), B.data_ptr(), C.data_ptr(), n, n, n, n, n, n, -1.0, 1.0, 1, int(syrk)) for A, B, C in zip(As, Bs, Cs)]
+    # one launch of all 9 (the round-filling chunks would cut 8 + 1 and never split)
     prev = pa.kernel_gemm_splitk(1)
+    prev_fill = pa.kernel_gemm_chunk_fill(0)
+    pa.kernel_gemm_launch_log(True, reset=True)
     try:
         assert pa.kernel_dgemm_batch(descs, _stream()) == 0
         torch.cuda.synchronize()
+        log = pa.kernel_gemm_launch_log()
     finally:
+        pa.kernel_gemm_launch_log(False, reset=True)
+        pa.kernel_gemm_chunk_fill(prev_fill)
         pa.kernel_gemm_splitk(prev)
+    assert len(log) == 1, log
+    assert (log[0]["BM"], log[0]["descs"], log[0]["ksplit"]) == (128, cnt, 4), log
+    assert log[0]["total_tiles"] == 576 and log[0]["main_tiles"] < 576, log
     low = torch.tril(torch.ones(n, n, dtype=torch.bool, device=dev))
     for C, ref, c0 in zip(Cs, refs, C0):
         if syrk:
