@@ -100,13 +100,6 @@ struct GemmDesc {
   // max|W|: a gated descriptor has beta 0 and never reads Cin as C) exceeds
   // the launch's limit
   uint8_t gate;
-  // 1: C is also the A operand (B := B op(W), the panel solve in place, op(B)
-  // upper triangular): the column blocks of a row run right to left in
-  // dispatch order, and a workgroup writes its block only after the ones to
-  // its right (which read it) finished; C2 then points to the per-row-block
-  // counters of this descriptor (unsigned, zero between launches), not a
-  // second output
-  uint8_t inplace;
   // optional (zero = off): beta scales Cin (ld ldcin) instead of C, and C2 (ld
   // ldc2) -= every value written to C (fused "W = A1 + V^T A2" / "A1 -= T^T W")
   int ldcin, ldc2;
@@ -228,15 +221,13 @@ int trsm_estimate_route(int on);
 // [0] estimates published by tile POTRFs, [1] panel decisions taken on the
 // host, [2] panels left to the device-side gate
 void trsm_estimate_stats(uint64_t out[3], bool reset);
-// in-place panel-solve W-GEMM (PARSEC_TRSM_INPLACE): on (1) / off (0), < 0 queries; returns the previous setting
-int trsm_inplace(int set);
 // a device buffer was (re)allocated: drop a panel estimate keyed by its address
 void trsm_estimate_forget(const void* p);
 double trsm_estimate_lookup(const void* p);
 std::vector<uintptr_t> trsm_estimate_known();
-// What the host decided for one grouped-DGEMM launch (launch_gemm_shape): the
-// tile shape, the operand mode, the tile / workgroup counts and the kernel
-// variant that went out.
+// What the host decides for one grouped-DGEMM launch: the tile shape, the
+// operand mode, the tile / workgroup counts and the kernel. The launch is
+// issued from this record, and the launch log keeps it.
 struct GemmLaunchRecord {
   int bm, bn;
   int descs;        // descriptors of the launch
@@ -247,11 +238,17 @@ struct GemmLaunchRecord {
   int pad_bytes;    // extra dynamic LDS (one bulk workgroup per CU)
   uint8_t transA, transB;
   uint8_t full;     // unchecked loads
-  uint8_t epilogue; // 0 plain (C preload when |alpha| = 1), 1 atomic, 2 late C
-  uint8_t rotated, direct_lds, persistent;
-  uint8_t ordered;  // in-place descriptors: tiles in dispatch order
+  uint8_t epilogue; // 0 plain (C preload when |alpha| = 1), 1 atomic
+  uint8_t rotated;  // rotated k loop (gemm_mainloop)
   uint8_t pipelined; // rotated loop with the pinned body (gemm_pipeline)
 };
+// The launches launch_gemm_batch would issue for these descriptors on `slots`
+// resident 128 x 128 workgroups under the current policy settings, in order,
+// to out (room for n); returns their number. one_per_cu: a padded bulk launch
+// (half the slots), bulk_yield / claim: as a yielding bulk stream or a
+// claiming critical stream (claim >= 2) launches. Host code only: no device is
+// touched and no descriptor pointer is dereferenced.
+int gemm_launch_plan(const GemmDesc* descs, int n, int slots, bool one_per_cu, bool bulk_yield, int claim, GemmLaunchRecord* out);
 constexpr int kGemmLaunchLogSize = 64;
 // Per-thread record of the last kGemmLaunchLogSize grouped-DGEMM launches,
 // written only while switched on: on 1 / 0, < 0 queries; returns the previous setting.

@@ -2,7 +2,7 @@
 //
 //  * Grouped DGEMM / DSYRK (lower) on v_mfma_f64_16x16x4f64: ONE launch runs every
 //    ready GEMM-shaped tile task of a scheduling round, so 512^2 tiles still fill
-//    the 256 CUs. Two tilings: 128x128 (4 waves x 64x64, 16 accumulators per wave)
+//    the 256 CUs. Two tilings: 128x128 (8 waves x 64x32, 8 accumulators per wave)
 //    for big batches and 64x64 for small ones. Workgroups are remapped so a task's
 //    tiles stay on one XCD (its operands stay in that XCD's 4 MiB L2).
 //    Two k loops for the full, register-staged, double-buffered launches
@@ -52,11 +52,6 @@ struct GemmBatchArgs {
   int claim; // critical-path launch: claim the CUs (bulk waves there pause)
   int yield; // bulk launch: pause while the CU hosts claimed critical work
   int total_tiles;
-  // staggered start (> 0): tiles [0, stagger) run as two K-halves, the first
-  // halves interleaved with whole tiles in the first round, the second halves
-  // last, both added into C (beta 1) -- workgroups then finish out of phase, so
-  // the C read / write bursts of a round overlap other workgroups' MFMA work
-  int stagger;
   // split-K tail: workgroups [main_tiles, grid) each take 1/ksplit of the K range
   // of one of the last (total_tiles - main_tiles) tiles and add alpha * partial
   // into C with f64 atomics (beta == 1 for every descriptor of such a launch)
@@ -78,6 +73,7 @@ static thread_local int t_launch_prio = 0;
 // 8 KB pads a workgroup to 82 KB, so a CU holds ONE bulk GEMM workgroup and
 // keeps room for a critical-path tile-POTRF step workgroup (78 KB)
 static thread_local int t_launch_pad = 0;
+constexpr int kBulkPadBytes = 8192;
 #define PARSEC_WAVE_PRIO(p) do { if (p) __builtin_amdgcn_s_setprio(2); } while (0)
 // critical-path launch of this thread: its workgroups claim their CUs
 static thread_local int t_launch_claim = 0;
@@ -148,24 +144,15 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
 // FULL: every descriptor of the launch is a whole number of BM x BN x BK tiles
 // with 16-byte aligned operands (the host checks), so the k loop carries no
 // bounds checks and no divergent control flow around its loads.
-// NBUF = 2: double-buffered LDS, one barrier per k-tile; NBUF = 1: one LDS
-// buffer (half the LDS, two barriers per k-tile) for deeper BK.
-// PF = 2 (NBUF 2 only): two k-tiles in flight in registers (loaded two compute
-// phases before their LDS store) for the one-workgroup-per-CU regime of the
-// DPOTRF bulk streams, where one k-tile of MFMA work per wave does not cover an
-// HBM miss.
+// The LDS k-tiles are double-buffered (one barrier per k-tile) and staged
+// through registers.
 // EPI = 1: the epilogue adds alpha * acc into C with no-return f64 atomics
 // performed at the memory side (beta == 1 for every descriptor of the launch):
 // the accumulators start from zero (no C preload), nothing of C is read by the
 // waves, and the wave does not wait for the update -- C traffic leaves the MFMA
 // timeline of the workgroup. Each element gets one add per tile (or per K chunk
 // of a split tile), so the result does not depend on timing.
-// EPI = 2: late C. The accumulators start from zero and C is read into its own
-// registers right behind the first A / B tile; the loads retire under the first
-// k-tile's MFMA work instead of in front of it, and the epilogue forms
-// alpha AB + beta C from registers (a pure store). Needs the register budget of
-// two waves per SIMD (launched with one workgroup per CU).
-// ML = 1 (FULL, !DL, NBUF 2, PF 1, !INPL only): the rotated k loop. The k loop
+// ML = 1 (FULL only): the rotated k loop. The k loop
 // is shifted by one kk-group (4 of k) and the MFMA fragments live in two
 // register sets: the fragments of group g + 1 are read while group g is
 // multiplied, the last group of a k-tile is multiplied behind the k-tile
@@ -184,11 +171,11 @@ __device__ __forceinline__ int xcd_remap(int b, int nwg) {
 // (sched_group_barrier), the reads of the last group a whole group in front
 // of the k-tile barrier, and group 0 of the next k-tile right behind it, in
 // front of the held-back MFMAs. No yield poll: such launches keep ML = 1.
-template <int BM, int BN, int BK, int WM, int WN, bool TRANSA, bool TRANSB, bool FULL, int NBUF, int PF, int EPI, bool DL = false, bool INPL = false, int ML = 0>
-__device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, int ks, int nsplit, double (&As)[NBUF][BK][BM + (((BM % 32) == 16) ? 0 : 16)],
-                                          double (&Bs)[NBUF][BK][BN + (((BN % 32) == 16) ? 0 : 16)]) {
-  static_assert(PF == 1 || NBUF == 2, "two tiles in flight need the double-buffered LDS");
-  static_assert(ML == 0 || (FULL && !DL && NBUF == 2 && PF == 1 && !INPL), "rotated k loop: full, register-staged, double-buffered tiles only");
+template <int BM, int BN, int BK, int WM, int WN, bool TRANSA, bool TRANSB, bool FULL, int EPI, int ML>
+__device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, int ks, int nsplit, double (&As)[2][BK][BM + (((BM % 32) == 16) ? 0 : 16)],
+                                          double (&Bs)[2][BK][BN + (((BN % 32) == 16) ? 0 : 16)]) {
+  static_assert(EPI == 0 || EPI == 1, "plain or atomic epilogue");
+  static_assert(ML == 0 || FULL, "rotated k loop: full tiles only");
   constexpr bool ROT = ML == 1;
   constexpr bool PIPE = ML == 2;
   constexpr int NT = WM * WN * 64;
@@ -200,8 +187,7 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
   const GemmDesc& d = args.d[di];
   const int local = tile - args.tile_start[di];
   const int mt = (d.m + BM - 1) / BM;
-  const int nt = (d.n + BN - 1) / BN;
-  const int tm = local % mt, tn = (INPL && d.inplace) ? nt - 1 - local / mt : local / mt;
+  const int tm = local % mt, tn = local / mt;
   const int m0 = tm * BM, n0 = tn * BN;
   if (d.lower_only && n0 > m0 + BM - 1) return;
   if (d.gate) {
@@ -247,9 +233,8 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
   constexpr int B_PAIRS = BN * BK / 2 / NT;
   static_assert(A_PAIRS >= 1 && B_PAIRS >= 1, "tile too small");
   double2_t ra[A_PAIRS], rb[B_PAIRS];
-  double2_t ra2[PF == 2 ? A_PAIRS : 1], rb2[PF == 2 ? B_PAIRS : 1];
 
-  auto load_tile_to = [&](int k0, double2_t* ra, double2_t* rb) {
+  auto load_tile = [&](int k0) {
 #pragma unroll
     for (int e = 0; e < A_PAIRS; ++e) {
       int idx = tid + NT * e;
@@ -301,7 +286,6 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
       }
     }
   };
-  auto load_tile = [&](int k0) { load_tile_to(k0, ra, rb); };
   // Operands loaded as k-pairs (op(A) = A^T, op(B) = B): LDS holds them
   // m- / n-major with k contiguous, rows of BK + 1 doubles inside the same
   // buffer. The fragment reads (ds_read2_b64: 16-lane groups, banks mod 32)
@@ -316,7 +300,7 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
   constexpr bool KB = !TRANSB && BN * KS <= BK * (BN + (((BN % 32) == 16) ? 0 : 16));
   auto a_km = [&](int buf) { return &As[buf][0][0]; };
   auto b_km = [&](int buf) { return &Bs[buf][0][0]; };
-  auto store_tile_from = [&](int buf, const double2_t* ra, const double2_t* rb) {
+  auto store_tile = [&](int buf) {
 #pragma unroll
     for (int e = 0; e < A_PAIRS; ++e) {
       int idx = tid + NT * e;
@@ -350,7 +334,6 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
       }
     }
   };
-  auto store_tile = [&](int buf) { store_tile_from(buf, ra, rb); };
   const int fr = lane & 15, fk = lane >> 4;
   auto mma_tile = [&](int cur) {
     if (args.yield && tid < 64) {
@@ -385,66 +368,6 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
   // beta's operand: C itself or a separate input (Cin)
   const double* __restrict__ Cr = d.Cin ? d.Cin : C;
   const int ldcr = d.Cin ? d.ldcin : ldc;
-  constexpr bool LATE = EPI == 2;
-  const bool late = LATE && FULL && !split && d.beta != 0.0;
-  double4_t cr[LATE ? FN : 1][LATE ? FM : 1];
-  if constexpr (DL) {
-    // Direct-to-LDS k-tiles (global_load_lds_dwordx4): for op(A) = A and
-    // op(B) = B^T a k-row of the A (B) tile is 128 contiguous doubles in memory
-    // and in LDS, i.e. exactly one wave-wide 16-byte-per-lane DMA, so the tiles
-    // skip the VGPR staging and the ds_write pass; the DMA of k-tile kt + 1
-    // runs under the MFMAs of k-tile kt (one barrier per k-tile).
-    static_assert(!TRANSA && TRANSB && FULL && (NBUF == 2 || NBUF == 3) && PF == 1 && BM == 128 && BN == 128 && !LATE, "direct-LDS tiles: NT operands, full 128x128 tiles");
-    constexpr int NW = NT / 64;
-    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-    auto dl_tile = [&](int k0, int buf) {
-#pragma unroll
-      for (int e = 0; e < BK / NW; ++e) {
-        const int kk = wave_u + NW * e;
-        __builtin_amdgcn_global_load_lds((const void*)(A + (size_t)(k0 + kk) * lda + m0 + 2 * lane),
-                                         (__attribute__((address_space(3))) void*)&As[buf][kk][0], 16, 0, 0);
-        __builtin_amdgcn_global_load_lds((const void*)(B + (size_t)(k0 + kk) * ldb + n0 + 2 * lane),
-                                         (__attribute__((address_space(3))) void*)&Bs[buf][kk][0], 16, 0, 0);
-      }
-    };
-    dl_tile(0, 0);
-    if (preload && d.beta != 0.0) {
-      const double cs = d.beta / d.alpha;
-#pragma unroll
-      for (int i = 0; i < FN; ++i)
-#pragma unroll
-        for (int j = 0; j < FM; ++j) {
-          const double* p = Cr + (size_t)(n0 + wn * WTN + i * 16 + fk) * ldcr + (m0 + wm * WTM + j * 16 + fr);
-#pragma unroll
-          for (int r = 0; r < 4; ++r) acc[i][j][r] = cs * p[(size_t)4 * r * ldcr];
-        }
-    }
-    if constexpr (NBUF == 2) {
-      for (int kt = 0; kt < nkt; ++kt) {
-        const int cur = kt & 1;
-        __builtin_amdgcn_s_waitcnt(0);  // this wave's DMA of k-tile kt has landed
-        __syncthreads();                 // ... every wave's; and buffer cur ^ 1 is free again
-        if (kt + 1 < nkt) dl_tile((kt + 1) * BK, cur ^ 1);
-        mma_tile(cur);
-      }
-    } else {
-      // three buffers: k-tile kt + 2 is requested while kt is multiplied (two
-      // k-tiles of DMA in flight to cover the memory latency under load)
-      constexpr int PER_TILE = 2 * (BK / NW);  // DMA instructions per wave per k-tile
-      static_assert(PER_TILE < 16, "vmcnt field");
-      if (nkt > 1) dl_tile(BK, 1);
-      int cur = 0, nxt = 2;
-      for (int kt = 0; kt < nkt; ++kt) {
-        if (kt + 1 < nkt) __builtin_amdgcn_s_waitcnt(PER_TILE | (7 << 4) | (15 << 8));  // only k-tile kt + 1 may still be in flight
-        else __builtin_amdgcn_s_waitcnt(0);
-        __syncthreads();  // every wave's k-tile kt landed; buffer (kt + 2) % 3 = (kt - 1) % 3 is free again
-        if (kt + 2 < nkt) dl_tile((kt + 2) * BK, nxt);
-        mma_tile(cur);
-        cur = cur == 2 ? 0 : cur + 1;
-        nxt = nxt == 2 ? 0 : nxt + 1;
-      }
-    }
-  } else {
   // ROT: global addresses of the k loop = one uniform base per operand, advanced
   // by a k-tile per load, plus per-thread element offsets fixed here (the
   // plain loop recomputes (size_t)gk * lda per load and k-tile)
@@ -500,16 +423,6 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
   if constexpr (PIPE) load_next32();
   else if constexpr (ROT) load_next();
   else load_tile(0);
-  if (LATE && late) {
-#pragma unroll
-    for (int i = 0; i < FN; ++i)
-#pragma unroll
-      for (int j = 0; j < FM; ++j) {
-        const double* p = Cr + (size_t)(n0 + wn * WTN + i * 16 + fk) * ldcr + (m0 + wm * WTM + j * 16 + fr);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) cr[i][j][r] = p[(size_t)4 * r * ldcr];
-      }
-  }
   if (preload && d.beta != 0.0) {
     const double cs = d.beta / d.alpha;
 #pragma unroll
@@ -698,54 +611,18 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
       ++kt;
     }
     k_tile(kt & 1, false, false);
-  } else if (PF == 2) {
-    // slot 1 (ra/rb) carries the odd tiles, slot 2 (ra2/rb2) the even ones
-    if (1 < nkt) load_tile_to(BK, ra, rb);
-    if (2 < nkt) load_tile_to(2 * BK, ra2, rb2);
-    __syncthreads();
-    for (int kt = 0; kt < nkt; kt += 2) {
-      mma_tile(0);                                  // tile kt
-      if (kt + 1 < nkt) store_tile_from(1, ra, rb);  // tile kt + 1 (loaded two phases ago)
-      __syncthreads();
-      if (kt + 3 < nkt) load_tile_to((kt + 3) * BK, ra, rb);
-      if (kt + 1 >= nkt) break;
-      mma_tile(1);                                    // tile kt + 1
-      if (kt + 2 < nkt) store_tile_from(0, ra2, rb2);  // tile kt + 2
-      __syncthreads();
-      if (kt + 4 < nkt) load_tile_to((kt + 4) * BK, ra2, rb2);
-    }
   } else {
-  __syncthreads();
-  for (int kt = 0; kt < nkt; ++kt) {
-    const int cur = NBUF == 2 ? (kt & 1) : 0;
-    if (kt + 1 < nkt) load_tile((kt + 1) * BK);
-    mma_tile(cur);
-    if (NBUF == 2) {
+    __syncthreads();
+    for (int kt = 0; kt < nkt; ++kt) {
+      const int cur = kt & 1;
+      if (kt + 1 < nkt) load_tile((kt + 1) * BK);
+      mma_tile(cur);
       if (kt + 1 < nkt) store_tile(cur ^ 1);
       __syncthreads();
-    } else if (kt + 1 < nkt) {
-      __syncthreads();
-      store_tile(0);
-      __syncthreads();
     }
   }
-  }
-  }  // DL
 
-  const double alpha = d.alpha, beta = (preload || late) ? 0.0 : d.beta;
-  // in place: the blocks to the right of this one in its row block (lower
-  // blockIdx: dispatched earlier, so waiting on them cannot deadlock) read it;
-  // write only after all of them finished. The wait is bounded: a lost
-  // signal degrades to a wrong result a test catches, never to a hung GPU.
-  unsigned* const rsync = (INPL && d.inplace) ? reinterpret_cast<unsigned*>(d.C2) + tm : nullptr;
-  if (rsync) {
-    if (tid == 0) {
-      const unsigned want = (unsigned)(nt - 1 - tn);
-      int spins = 0;
-      while (__hip_atomic_load(rsync, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) < want && spins++ < (1 << 19)) __builtin_amdgcn_s_sleep(8);
-    }
-    __syncthreads();
-  }
+  const double alpha = d.alpha, beta = preload ? 0.0 : d.beta;
 #pragma unroll
   for (int i = 0; i < FN; ++i)
 #pragma unroll
@@ -757,61 +634,32 @@ __device__ __forceinline__ void gemm_tile(const GemmBatchArgs& args, int tile, i
         if ((FULL || (gm < M && gn < N)) && (!d.lower_only || gm >= gn)) {
           double* p = C + (size_t)gn * ldc + gm;
           double v = alpha * acc[i][j][r];
-          if (LATE && late) v = fma(d.beta, cr[LATE ? i : 0][LATE ? j : 0][r], v);
           if (split || EPI == 1) {
             unsafeAtomicAdd(p, v);  // no-return global f64 add, performed at the memory side
             continue;
           }
           if (beta != 0.0) v += beta * Cr[(size_t)gn * ldcr + gm];
           *p = v;
-          if (d.C2 && !rsync) d.C2[(size_t)gn * d.ldc2 + gm] -= v;
+          if (d.C2) d.C2[(size_t)gn * d.ldc2 + gm] -= v;
         }
       }
     }
-  if (rsync) {
-    // signal the blocks to the left; the leftmost one (the last of its row)
-    // leaves the counter at zero for the next launch
-    __threadfence();
-    __syncthreads();
-    if (tid == 0) {
-      if (tn == 0) __hip_atomic_store(rsync, 0u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-      else __hip_atomic_fetch_add(rsync, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
   crit_release(args.claim);
 }
 
-template <int BM, int BN, int BK, int WM, int WN, bool TRANSA, bool TRANSB, bool FULL, int NBUF = 2, int OCC = WM * WN / 2, int PF = 1, int EPI = 0, bool DL = false, bool INPL = false, int ML = 0>
-__global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(OCC))) void dgemm_batch_kernel(const GemmBatchArgs args) {
+template <int BM, int BN, int BK, int WM, int WN, bool TRANSA, bool TRANSB, bool FULL, int EPI = 0, int ML = 0>
+__global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(WM * WN / 2))) void dgemm_batch_kernel(const GemmBatchArgs args) {
   constexpr int PADM = ((BM % 32) == 16) ? 0 : 16;
   constexpr int PADN = ((BN % 32) == 16) ? 0 : 16;
-  __shared__ __attribute__((aligned(16))) double As[NBUF][BK][BM + PADM];
-  __shared__ __attribute__((aligned(16))) double Bs[NBUF][BK][BN + PADN];
+  __shared__ __attribute__((aligned(16))) double As[2][BK][BM + PADM];
+  __shared__ __attribute__((aligned(16))) double Bs[2][BK][BN + PADN];
   PARSEC_WAVE_PRIO(args.prio);
   // Workgroups [0, main_tiles) own whole tiles (XCD-aware order); the ones
   // dispatched last split the K range of the tail tiles (wave quantisation:
   // a 606-tile launch on 512 slots would otherwise run a 94-tile second round)
   int tile, ks = 0, nsplit = 1;
-  if (args.stagger > 0) {
-    const int S = args.stagger, total = args.total_tiles;
-    const int p = xcd_remap(blockIdx.x, total + S);
-    if (p < 2 * S) {
-      if (p & 1) {
-        tile = S + (p >> 1);
-      } else {
-        tile = p >> 1;
-        nsplit = 2;
-      }
-    } else if (p < total) {
-      tile = p;
-    } else {
-      tile = p - total;
-      nsplit = 2;
-      ks = 1;
-    }
-  } else if ((int)blockIdx.x < args.main_tiles) {
-    // INPL: tiles in dispatch order (in-place descriptors wait on lower blockIdx)
-    tile = INPL ? (int)blockIdx.x : xcd_remap(blockIdx.x, args.main_tiles);
+  if ((int)blockIdx.x < args.main_tiles) {
+    tile = xcd_remap(blockIdx.x, args.main_tiles);
   } else {
     const int u = blockIdx.x - args.main_tiles;
     nsplit = args.ksplit;
@@ -819,27 +667,7 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(OC
     ks = u % nsplit;
   }
   if (tile >= args.total_tiles) return;
-  gemm_tile<BM, BN, BK, WM, WN, TRANSA, TRANSB, FULL, NBUF, PF, EPI, DL, INPL, ML>(args, tile, ks, nsplit, As, Bs);
-}
-
-// Persistent form: a grid of (at most) one round of resident workgroups walks
-// the launch's tiles, workgroup b taking every G-th tile of its XCD's
-// contiguous range, so a workgroup's next tile starts without a new dispatch
-// and, with the atomic epilogue, without waiting for its C update to land.
-template <int BM, int BN, int BK, int WM, int WN, bool TRANSA, bool TRANSB, bool FULL, int NBUF = 2, int OCC = WM * WN / 2, int PF = 1, int EPI = 0>
-__global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(OCC))) void dgemm_persist_kernel(const GemmBatchArgs args) {
-  constexpr int PADM = ((BM % 32) == 16) ? 0 : 16;
-  constexpr int PADN = ((BN % 32) == 16) ? 0 : 16;
-  __shared__ double As[NBUF][BK][BM + PADM];
-  __shared__ double Bs[NBUF][BK][BN + PADN];
-  PARSEC_WAVE_PRIO(args.prio);
-  const int G = gridDim.x, b = blockIdx.x, T = args.total_tiles;
-  const int x = b % 8, nx = G / 8 + (x < G % 8 ? 1 : 0), i = b / 8;  // workgroups b = x, x + 8, ... share XCD x
-  const int t0 = (int)((long long)T * x / 8), t1 = (int)((long long)T * (x + 1) / 8);
-  for (int tile = t0 + i; tile < t1; tile += nx) {
-    gemm_tile<BM, BN, BK, WM, WN, TRANSA, TRANSB, FULL, NBUF, PF, EPI>(args, tile, 0, 1, As, Bs);
-    __syncthreads();  // the LDS tiles are reused by the next tile's prologue
-  }
+  gemm_tile<BM, BN, BK, WM, WN, TRANSA, TRANSB, FULL, EPI, ML>(args, tile, ks, nsplit, As, Bs);
 }
 
 // ========================================================= diag blocks (4 waves)
@@ -1341,18 +1169,64 @@ __global__ __launch_bounds__(kTrsmThreads) void dtrsm_left_kernel(const TrsmLeft
 }
 
 // ================================================================ launchers
-static int g_gemm_tile_policy = -1;  // -1 unset, 0 auto, 64, 128
-static int g_gemm_variant = -1;      // big-tile kernel shape (PARSEC_GEMM_VARIANT)
-static int g_gemm_full = -1;         // PARSEC_GEMM_FULL=0 disables the unchecked fast path
-static int g_gemm_big_tiles = 384;   // PARSEC_GEMM_BIG_TILES: 128x128 tiles in a launch to pick the big kernel
-static int g_gemm_splitk = -1;       // PARSEC_GEMM_SPLITK=0 disables the split-K tail of the 128x128 kernel
-static int g_gemm_mainloop = -1;     // PARSEC_GEMM_MAINLOOP: k loop of the full register-staged launches, 0 plain, 1 rotated (default)
-static int g_gemm_pipeline = -1;     // PARSEC_GEMM_PIPELINE: body of the rotated k loop, 0 compiler-scheduled, 1 pinned (gemm_tile ML = 2, default)
-static int g_gemm_slots = 512;       // resident 128x128 workgroups (2 per CU): one round of the big kernel
-static int g_gemm_chunk_fill = -1;   // PARSEC_GEMM_CHUNK_FILL=0: fixed 40-descriptor launches
+// Every knob of the grouped-GEMM dispatch: read from the environment once
+// (gemm_policy_init, no device needed), changed afterwards by the setters below.
+struct GemmPolicy {
+  int tile = 0;          // PARSEC_GEMM_TILE: 0 auto, 64, 128
+  int full = 1;          // PARSEC_GEMM_FULL=0 disables the unchecked fast path
+  int big_tiles = 384;   // PARSEC_GEMM_BIG_TILES: 128x128 tiles in a launch to pick the big kernel
+  int splitk = 1;        // PARSEC_GEMM_SPLITK=0 disables the split-K tail of the 128x128 kernel (tests/test_headline_gpu.py, profiles/r2_bench_ab_fill_splitk.log)
+  int mainloop = 1;      // PARSEC_GEMM_MAINLOOP: k loop of the full launches, 0 plain, 1 rotated (profiles/gemm_rotated_mainloop.txt, tests/test_gemm_mainloop_gpu.py)
+  int pipeline = 1;      // PARSEC_GEMM_PIPELINE: body of the rotated k loop, 0 compiler-scheduled, 1 pinned (gemm_tile ML = 2; profiles/gemm_pipelined_mainloop.txt, tests/test_gemm_pipeline_gpu.py)
+  int chunk_fill = 1;    // PARSEC_GEMM_CHUNK_FILL=0: fixed 40-descriptor launches
+  int slots = 0;         // PARSEC_GEMM_SLOTS: resident 128x128 workgroups, one round of the big kernel; 0 = two per CU of the device
+  // PARSEC_GEMM_EPI: the atomic epilogue 1 always, 0 never, -1 when every
+  // descriptor has K >= 1024: 40 x 1024^3 61.6 -> 63.9 TF, 16 x 1024^3 57.9 ->
+  // 58.9 TF, but 32 x 512^3 51.3 -> 47.5 TF (half the flops per memory-side
+  // add) -- profiles/r5_gemm_epilogue.txt
+  int epi = -1;
+  bool pad_test = false;   // PARSEC_GEMM_PAD_TEST=1: parsec_amd_dgemm_batch launches like a DPOTRF bulk stream
+  bool pad_debug = false;  // PARSEC_GEMM_PAD_DEBUG: say so once when a padded launch goes out
+};
+static GemmPolicy gemm_policy_init() {
+  GemmPolicy p;
+  auto num = [](const char* name, int& v) {
+    if (const char* e = getenv(name)) v = atoi(e);
+  };
+  num("PARSEC_GEMM_TILE", p.tile);
+  num("PARSEC_GEMM_FULL", p.full);
+  num("PARSEC_GEMM_BIG_TILES", p.big_tiles);
+  num("PARSEC_GEMM_SPLITK", p.splitk);
+  num("PARSEC_GEMM_MAINLOOP", p.mainloop);
+  num("PARSEC_GEMM_PIPELINE", p.pipeline);
+  num("PARSEC_GEMM_CHUNK_FILL", p.chunk_fill);
+  num("PARSEC_GEMM_SLOTS", p.slots);
+  num("PARSEC_GEMM_EPI", p.epi);
+  p.mainloop = p.mainloop != 0;
+  p.pipeline = p.pipeline != 0;
+  if (getenv("PARSEC_GEMM_SLOTS")) p.slots = std::max(1, p.slots);
+  if (p.epi != 0 && p.epi != 1) p.epi = -1;
+  int pad_test = 0;
+  num("PARSEC_GEMM_PAD_TEST", pad_test);
+  p.pad_test = pad_test != 0;
+  p.pad_debug = getenv("PARSEC_GEMM_PAD_DEBUG") != nullptr;
+  return p;
+}
+static GemmPolicy& gemm_policy() {
+  static GemmPolicy p = gemm_policy_init();
+  return p;
+}
 // resident 128x128 workgroups of the launch being issued: half when bulk
 // launches are padded to one workgroup per CU (t_launch_pad)
-static inline int gemm_slots() { return t_launch_pad ? std::max(1, g_gemm_slots / 2) : g_gemm_slots; }
+static int gemm_slots() {
+  static const int device_slots = [] {
+    int dev = 0, ncu = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) return 2 * ncu;
+    return 512;
+  }();
+  const int slots = gemm_policy().slots > 0 ? gemm_policy().slots : device_slots;
+  return t_launch_pad ? std::max(1, slots / 2) : slots;
+}
 
 // The pinned body addresses an operand as a uniform base plus a 32-bit
 // per-thread byte offset that spans the columns of the stored operand a k-tile
@@ -1369,305 +1243,21 @@ static thread_local bool t_gemm_log_on = false;
 static thread_local GemmLaunchRecord t_gemm_log[kGemmLaunchLogSize];
 static thread_local unsigned t_gemm_log_count = 0;  // records written since the last reset
 
-template <int BM, int BN, int BK, int WM, int WN, int NBUF, int OCC = WM * WN / 2, int PF = 1>
-static void launch_gemm_shape(GemmBatchArgs& a, const GemmDesc* descs, int n, hipStream_t stream) {
-  a.prio = t_launch_prio;
-  a.claim = t_launch_claim >= 2;
-  a.yield = t_launch_yield;
-  a.gate_limit = parsec::trsm_inverse_limit();
-  int total = 0;
-  bool full = g_gemm_full != 0;
-  for (int i = 0; i < n; ++i) {
-    const GemmDesc& g = descs[i];
-    full = full && g.m % BM == 0 && g.n % BN == 0 && g.k > 0 && g.k % BK == 0 && (g.lda | g.ldb) % 2 == 0 &&
-           ((uintptr_t)g.A | (uintptr_t)g.B) % 16 == 0;
-    a.d[i] = g;
-    a.tile_start[i] = total;
-    total += ((g.m + BM - 1) / BM) * ((g.n + BN - 1) / BN);
-  }
-  a.tile_start[n] = total;
-  a.total_tiles = total;
-  a.main_tiles = total;
-  a.ksplit = 1;
-  a.stagger = 0;
-  if (total == 0) return;
-  int grid_size = total;
-  const int slots = gemm_slots();
-  static const int stagger_env = getenv("PARSEC_GEMM_STAGGER") ? atoi(getenv("PARSEC_GEMM_STAGGER")) : 0;
-  bool ordered = false;  // in-place descriptors: tiles in dispatch order, no remap / stagger / split / persistent / direct-LDS
-  for (int i = 0; i < n; ++i) ordered = ordered || descs[i].inplace;
-  if (ordered) a.stagger = -1;
-  if (!ordered && BM == 128 && stagger_env > 0 && total >= 2 * slots) {
-    bool ok = true;
-    for (int i = 0; ok && i < n; ++i)
-      ok = descs[i].beta == 1.0 && !descs[i].a_lower && !descs[i].b_upper && !descs[i].Cin && !descs[i].C2 && !descs[i].gate && descs[i].k >= 2 * BK;
-    if (ok) {
-      a.stagger = slots / 2;
-      grid_size = total + a.stagger;
-    }
-  }
-  if (BM == 128 && g_gemm_splitk != 0 && total > slots && a.stagger == 0) {
-    // the last partial round of workgroups: split its tiles' K range so it
-    // finishes in 1/s of a tile time; needs beta == 1 (partials are added into C)
-    // and >= 256 of K per chunk (fewer flops per added byte would be bound by
-    // the chip's f64 atomic rate)
-    const int tail = total % slots;
-    int kmin = 1 << 30;
-    bool ok = tail > 0 && 2 * tail <= slots;
-    for (int i = 0; ok && i < n; ++i) {
-      ok = descs[i].beta == 1.0 && !descs[i].a_lower && !descs[i].b_upper && !descs[i].Cin && !descs[i].C2;
-      kmin = std::min(kmin, descs[i].k);
-    }
-    const int s = ok ? std::min({slots / std::max(tail, 1), kmin / 256, 8}) : 1;
-    if (s >= 2) {
-      a.main_tiles = total - tail;
-      a.ksplit = s;
-      grid_size = a.main_tiles + tail * s;
-    }
-  }
-  const int mode = (descs[0].transA ? 2 : 0) | (descs[0].transB ? 1 : 0);
-  // atomic epilogue: every descriptor accumulates into C (beta 1, no separate
-  // Cin / C2). PARSEC_GEMM_EPI = 1 always, 0 never, -1 (default) when every
-  // descriptor has K >= 1024: 40 x 1024^3 61.6 -> 63.9 TF, 16 x 1024^3 57.9 ->
-  // 58.9 TF, but 32 x 512^3 51.3 -> 47.5 TF (half the flops per memory-side
-  // add) -- profiles/r5_gemm_epilogue.txt. Persistent grid (PARSEC_GEMM_PERSIST=1,
-  // off: -5..-8 % with one workgroup per CU): one round of resident workgroups
-  // walks the tiles (no split-K tail, no stagger).
-  const size_t pad = BM == 128 ? (size_t)t_launch_pad : 0;
-  static const int epi_env = getenv("PARSEC_GEMM_EPI") ? atoi(getenv("PARSEC_GEMM_EPI")) : -1;
-  static const int persist_env = getenv("PARSEC_GEMM_PERSIST") ? atoi(getenv("PARSEC_GEMM_PERSIST")) : 0;
-  bool epi = epi_env != 0 && epi_env != 2 && full;
-  for (int i = 0; epi && i < n; ++i) epi = descs[i].beta == 1.0 && !descs[i].Cin && !descs[i].C2 && (epi_env > 0 || descs[i].k >= 1024);
-  // late C (EPI 2) on the one-workgroup-per-CU bulk launches that do not take
-  // the atomic epilogue: PARSEC_GEMM_LATE_C = 1 (default 0 until measured)
-  static const int late_env = getenv("PARSEC_GEMM_LATE_C") ? atoi(getenv("PARSEC_GEMM_LATE_C")) : 0;
-  const bool late = BM == 128 && full && !epi && (epi_env == 2 || late_env > 0) && pad;
-  const bool persist = persist_env != 0 && full && BM == 128 && a.stagger == 0 && total > slots;
-  // direct-to-LDS k-tiles for the NT bulk GEMM (PARSEC_GEMM_DLDS=1; off until measured)
-  static const int dl_env = getenv("PARSEC_GEMM_DLDS") ? atoi(getenv("PARSEC_GEMM_DLDS")) : 0;
-  const bool dl = dl_env != 0 && !late && a.stagger == 0;
-  // rotated k loop (gemm_tile ML = 1) for the full, register-staged, double-buffered launches
-  const bool rot = g_gemm_mainloop == 1;
-  // its pinned body (ML = 2): no yield poll or CU claim, 32-bit per-thread operand offsets
-  bool pipe = rot && g_gemm_pipeline == 1 && !a.yield && !a.claim;
-  for (int i = 0; pipe && i < n; ++i) pipe = gemm_pipeline_fits(BM, BN, BK, descs[i].transA, descs[i].transB, descs[i].lda, descs[i].ldb) != 0;
-  if (persist) {
-    a.main_tiles = total;
-    a.ksplit = 1;
-    grid_size = slots;
-  }
-  const dim3 grid(grid_size), block(WM * WN * 64);
-  // the kernel that goes out, noted beside its launch
-  auto note = [&](bool k_full, int k_epi, bool k_rot, bool k_dl, bool k_persist, bool k_pipe = false) {
-    if (!t_gemm_log_on) return;
-    GemmLaunchRecord& r = t_gemm_log[t_gemm_log_count++ % kGemmLaunchLogSize];
-    r.bm = BM; r.bn = BN;
-    r.descs = n;
-    r.total_tiles = total; r.main_tiles = a.main_tiles; r.ksplit = a.ksplit;
-    r.grid = grid_size;
-    r.pad_bytes = (int)pad;
-    r.transA = (mode & 2) != 0; r.transB = (mode & 1) != 0;
-    r.full = k_full; r.epilogue = (uint8_t)k_epi;
-    r.rotated = k_rot; r.direct_lds = k_dl; r.persistent = k_persist;
-    r.pipelined = k_pipe;
-    r.ordered = ordered;
-  };
-  if (pad) {
-    static bool said = false;
-    if (!said && getenv("PARSEC_GEMM_PAD_DEBUG")) {
-      said = true;
-      std::fprintf(stderr, "[gemm] bulk 128x128 launch with %zu extra LDS bytes (one workgroup per CU)\n", pad);
-    }
-  }
-#define PARSEC_GEMM_LAUNCH_E(TA, TB, E)                                                                                                      \
-  do {                                                                                                                                      \
-    if constexpr (!(TA) && (TB) && BM == 128 && BN == 128 && (NBUF == 2 || NBUF == 3) && PF == 1)                                          \
-      if (dl && full && !persist) {                                                                                                          \
-        note(true, E, false, true, false);                                                                                                   \
-        hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E, true>), grid, block, pad, stream, a);     \
-        break;                                                                                                                               \
-      }                                                                                                                                      \
-    if constexpr (NBUF == 2 && PF == 1)                                                                                                      \
-      if (pipe && full && !persist) {                                                                                                        \
-        note(true, E, true, false, false, true);                                                                                             \
-        hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E, false, false, 2>), grid, block, pad, stream, a); \
-        break;                                                                                                                               \
-      }                                                                                                                                      \
-    if constexpr (NBUF == 2 && PF == 1)                                                                                                      \
-      if (rot && full && !persist) {                                                                                                         \
-        note(true, E, true, false, false);                                                                                                   \
-        hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E, false, false, 1>), grid, block, pad, stream, a); \
-        break;                                                                                                                               \
-      }                                                                                                                                      \
-    note(full, full ? E : 0, false, false, persist);                                                                                         \
-    if (persist) hipLaunchKernelGGL((dgemm_persist_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E>), grid, block, pad, stream, a);  \
-    else if (full) hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, OCC, PF, E>), grid, block, pad, stream, a);  \
-    else hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, false, NBUF, OCC, PF, 0>), grid, block, pad, stream, a);          \
-  } while (0)
-#define PARSEC_GEMM_LAUNCH(TA, TB)                                                                                   \
-  do {                                                                                                              \
-    if constexpr (BM == 128) {                                                                                      \
-      if (late && !persist) {                                                                                       \
-        if constexpr (NBUF == 2 && PF == 1)                                                                         \
-          if (pipe) {                                                                                               \
-            note(true, 2, true, false, false, true);                                                                \
-            hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, 2, PF, 2, false, false, 2>), grid, block, pad, stream, a); \
-            break;                                                                                                  \
-          }                                                                                                         \
-        if constexpr (NBUF == 2 && PF == 1)                                                                         \
-          if (rot) {                                                                                                \
-            note(true, 2, true, false, false);                                                                      \
-            hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, 2, PF, 2, false, false, 1>), grid, block, pad, stream, a); \
-            break;                                                                                                  \
-          }                                                                                                         \
-        note(true, 2, false, false, false);                                                                         \
-        hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, NBUF, 2, PF, 2>), grid, block, pad, stream, a); \
-        break;                                                                                                      \
-      }                                                                                                             \
-    }                                                                                                               \
-    if (epi) PARSEC_GEMM_LAUNCH_E(TA, TB, 1);                                                                       \
-    else PARSEC_GEMM_LAUNCH_E(TA, TB, 0);                                                                           \
-  } while (0)
-  if (ordered) {
-    // in-place panel solve (launch_trsm_w_batch): NT descriptors, plain epilogue
-    if (mode != 1 || epi || late) fatal("in-place GEMM launch: NT descriptors with the plain epilogue only");
-    note(full, 0, false, false, false);
-    if (full) hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, false, true, true, NBUF, OCC, PF, 0, false, true>), grid, block, pad, stream, a);
-    else hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, false, true, false, NBUF, OCC, PF, 0, false, true>), grid, block, pad, stream, a);
-    return;
-  }
-  switch (mode) {
-    case 0: PARSEC_GEMM_LAUNCH(false, false); break;
-    case 1: PARSEC_GEMM_LAUNCH(false, true); break;
-    case 2: PARSEC_GEMM_LAUNCH(true, false); break;
-    default: PARSEC_GEMM_LAUNCH(true, true); break;
-  }
-#undef PARSEC_GEMM_LAUNCH
-#undef PARSEC_GEMM_LAUNCH_E
-}
-
-static void gemm_policy_init() {
-  if (g_gemm_tile_policy < 0) {
-    const char* e = getenv("PARSEC_GEMM_TILE");
-    g_gemm_tile_policy = e ? atoi(e) : 0;
-    e = getenv("PARSEC_GEMM_VARIANT");
-    g_gemm_variant = e ? atoi(e) : 0;
-    e = getenv("PARSEC_GEMM_FULL");
-    g_gemm_full = e ? atoi(e) : 1;
-    e = getenv("PARSEC_GEMM_BIG_TILES");
-    if (e) g_gemm_big_tiles = atoi(e);
-    e = getenv("PARSEC_GEMM_SPLITK");
-    g_gemm_splitk = e ? atoi(e) : 1;  // validated: tests/test_headline_gpu.py, profiles/r2_bench_ab_fill_splitk.log
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0)
-      g_gemm_slots = 2 * ncu;
-    e = getenv("PARSEC_GEMM_MAINLOOP");
-    g_gemm_mainloop = e ? (atoi(e) == 0 ? 0 : 1) : 1;  // measured: profiles/gemm_rotated_mainloop.txt, tests/test_gemm_mainloop_gpu.py
-    e = getenv("PARSEC_GEMM_PIPELINE");
-    g_gemm_pipeline = e ? (atoi(e) == 0 ? 0 : 1) : 1;  // measured: profiles/gemm_pipelined_mainloop.txt, tests/test_gemm_pipeline_gpu.py
-    e = getenv("PARSEC_GEMM_CHUNK_FILL");
-    g_gemm_chunk_fill = e ? atoi(e) : 1;
-    e = getenv("PARSEC_GEMM_SLOTS");
-    if (e) g_gemm_slots = std::max(1, atoi(e));
-  }
-}
-
-// Split-K tail of the 128x128 kernel on (1) / off (0), < 0 queries; returns the previous setting.
-int gemm_splitk(int on) {
-  gemm_policy_init();
-  const int prev = g_gemm_splitk;
-  if (on >= 0) g_gemm_splitk = on;
-  return prev;
-}
-
-// k loop of the full register-staged GEMM launches: 0 plain, 1 rotated, < 0 queries; returns the previous setting.
-int gemm_mainloop(int mode) {
-  gemm_policy_init();
-  const int prev = g_gemm_mainloop;
-  if (mode >= 0) g_gemm_mainloop = mode == 0 ? 0 : 1;
-  return prev;
-}
-
-// Body of the rotated k loop (consulted only when gemm_mainloop is 1): 0 compiler-scheduled, 1 pinned, < 0 queries; returns the previous setting.
-int gemm_pipeline(int mode) {
-  gemm_policy_init();
-  const int prev = g_gemm_pipeline;
-  if (mode >= 0) g_gemm_pipeline = mode == 0 ? 0 : 1;
-  return prev;
-}
-
-// Round-filling launch chunks on (1) / off (0), < 0 queries; returns the previous setting.
-int gemm_chunk_fill(int on) {
-  gemm_policy_init();
-  const int prev = g_gemm_chunk_fill;
-  if (on >= 0) g_gemm_chunk_fill = on != 0;
-  return prev;
-}
-
-int gemm_launch_log(int on) {
-  const int prev = t_gemm_log_on;
-  if (on >= 0) t_gemm_log_on = on != 0;
-  return prev;
-}
-
-int gemm_launch_log_read(GemmLaunchRecord* out, bool reset) {
-  const unsigned have = std::min<unsigned>(t_gemm_log_count, kGemmLaunchLogSize);
-  for (unsigned i = 0; i < have; ++i) out[i] = t_gemm_log[(t_gemm_log_count - have + i) % kGemmLaunchLogSize];
-  if (reset) t_gemm_log_count = 0;
-  return (int)have;
-}
-
-// Tile-size policy of the grouped GEMM (0 = auto, 64, 128); returns the previous one.
-int gemm_tile_policy(int p) {
-  gemm_policy_init();
-  const int prev = g_gemm_tile_policy;
-  if (p >= 0) g_gemm_tile_policy = p;
-  return prev;
-}
-
-static void launch_gemm_chunk(const GemmDesc* descs, int n, hipStream_t stream) {
-  gemm_policy_init();
-  GemmBatchArgs a;
-  a.count = n;
-  int t128 = 0;
-  bool big = true;
-  for (int i = 0; i < n; ++i) {
-    t128 += ((descs[i].m + 127) / 128) * ((descs[i].n + 127) / 128);
-    if (descs[i].m < 128 || descs[i].n < 128) big = false;
-  }
-  // PARSEC_CRIT_TILE=64 (measurement): critical-stream groups (the chain's
-  // TRSM / SYRK / column GEMMs) on 64x64 tiles -- four times the workgroups,
-  // each a quarter of the work, spread over more CUs beside the bulk kernels
-  static const int crit_tile = getenv("PARSEC_CRIT_TILE") ? atoi(getenv("PARSEC_CRIT_TILE")) : 0;
-  const bool use_big = (g_gemm_tile_policy == 128 || (g_gemm_tile_policy == 0 && big && t128 >= g_gemm_big_tiles)) && !(crit_tile == 64 && t_launch_prio);
-  if (!use_big) { launch_gemm_shape<64, 64, 16, 2, 2, 2>(a, descs, n, stream); return; }
-  switch (g_gemm_variant) {
-    case 6: launch_gemm_shape<128, 128, 16, 4, 2, 2>(a, descs, n, stream); break;
-    case 8: launch_gemm_shape<128, 128, 16, 2, 2, 2>(a, descs, n, stream); break;
-    // two k-tiles in flight (PF 2), 8 waves, up to 256 VGPRs: one workgroup per CU
-    case 9: launch_gemm_shape<128, 128, 16, 2, 4, 2, 2, 2>(a, descs, n, stream); break;
-    // the same at the default occupancy bound (128 VGPRs)
-    case 10: launch_gemm_shape<128, 128, 16, 2, 4, 2, 4, 2>(a, descs, n, stream); break;
-    // k-tiles of 32 (144 KB of LDS: one workgroup per CU, half the barriers per
-    // flop; with PARSEC_GEMM_DLDS the k-tiles go straight to LDS); measured 10 % slower
-    case 11: launch_gemm_shape<128, 128, 32, 2, 4, 2>(a, descs, n, stream); break;
-    // three LDS k-tile buffers (110 KB), only with PARSEC_GEMM_DLDS=1: two k-tiles of DMA in
-    // flight; measured 15 % slower than variant 0 (profiles/r5_gemm_direct_lds.txt)
-    case 12: launch_gemm_shape<128, 128, 16, 2, 4, 3>(a, descs, n, stream); break;
-    // 256 x 128 macro tiles, 8 waves of 64 x 64 (16 accumulators each, up to 256
-    // VGPRs + AGPRs: one workgroup per CU): a quarter fewer L2 -> LDS bytes per
-    // flop and twice the MFMA work between barriers; BK 16 (106 KB of LDS) or 8
-    // (53 KB). No room for a co-resident critical-path workgroup.
-    case 13: launch_gemm_shape<256, 128, 16, 4, 2, 2, 2>(a, descs, n, stream); break;
-    case 14: launch_gemm_shape<256, 128, 8, 4, 2, 2, 2>(a, descs, n, stream); break;
-    // default: 8 waves (2 x 4) of 64x32 per 128x128 tile, 126 VGPRs -> 4 waves per
-    // SIMD with two workgroups per CU (measured: DPOTRF 64k +4 %, 16k +7 % over
-    // the 4-wave 64x64-per-wave kernel = variant 8; profiles/r1_gemm_variants_v8.log;
-    // BK=32 single-buffer and 256x128 tiles (8 or 16 waves) measured no better:
-    // r1_gemm_variants_v4.log, r1_gemm_variants_v13.log)
-    default: launch_gemm_shape<128, 128, 16, 2, 4, 2>(a, descs, n, stream); break;
-  }
-}
+// ---- Decide. What launch_gemm_batch issues for a descriptor list is computed
+// here on the host alone, from the descriptors and an explicit environment; no
+// pointer is dereferenced and no device is asked.
+struct GemmPlanEnv {
+  GemmPolicy policy;
+  int slots;      // resident 128x128 workgroups of one round (already halved for a padded launch)
+  int pad_bytes;  // extra dynamic LDS of a 128x128 launch (one bulk workgroup per CU)
+  bool yield;     // bulk launch: the waves poll their CU's claim count
+  bool claim;     // critical launch: the workgroups claim their CUs
+};
+// one launch: its record and its descriptors, [first, first + rec.descs) of the regrouped list
+struct GemmLaunch {
+  GemmLaunchRecord rec;
+  int first;
+};
 
 // Descriptors per launch (<= kMaxGemmBatch, the kernel-argument limit): the cut
 // that fills whole rounds of resident 128x128 workgroups best. 40 tiles of
@@ -1688,20 +1278,76 @@ static int gemm_chunk_cut(Tiles128 tiles128, int n, int slots, bool fill_rounds)
   }
   return best_fill >= 0.0 ? best : cap;
 }
-static int gemm_chunk_size(const GemmDesc* d, int n) {
-  return gemm_chunk_cut([d](int i) { return ((d[i].m + 127) / 128) * ((d[i].n + 127) / 128); }, n, gemm_slots(), g_gemm_chunk_fill != 0);
-}
 int gemm_chunk_plan(const int* m, const int* n, int count, int slots, int* out) {
-  // no device needed: before the policies are read, the setting is the environment's
-  int fill = g_gemm_chunk_fill;
-  if (fill < 0) fill = getenv("PARSEC_GEMM_CHUNK_FILL") ? atoi(getenv("PARSEC_GEMM_CHUNK_FILL")) : 1;
   int cuts = 0;
   for (int s = 0; s < count;) {
-    const int c = gemm_chunk_cut([&](int i) { return ((m[s + i] + 127) / 128) * ((n[s + i] + 127) / 128); }, count - s, std::max(1, slots), fill != 0);
+    const int c = gemm_chunk_cut([&](int i) { return ((m[s + i] + 127) / 128) * ((n[s + i] + 127) / 128); }, count - s, std::max(1, slots),
+                                 gemm_policy().chunk_fill != 0);
     out[cuts++] = c;
     s += c;
   }
   return cuts;
+}
+
+// One launch of n descriptors of one operand mode: tile shape, kernel, grid.
+static GemmLaunchRecord gemm_plan_launch(const GemmDesc* descs, int n, const GemmPlanEnv& env) {
+  const GemmPolicy& p = env.policy;
+  GemmLaunchRecord r{};
+  int t128 = 0;
+  bool big = true;
+  for (int i = 0; i < n; ++i) {
+    t128 += ((descs[i].m + 127) / 128) * ((descs[i].n + 127) / 128);
+    if (descs[i].m < 128 || descs[i].n < 128) big = false;
+  }
+  // 128x128: 8 waves (2 x 4) of 64x32, 126 VGPRs -> 4 waves per SIMD with two
+  // workgroups per CU (profiles/r1_gemm_variants_v8.log); 64x64: 4 waves of 32x32
+  const bool use_big = p.tile == 128 || (p.tile == 0 && big && t128 >= p.big_tiles);
+  const int BM = use_big ? 128 : 64, BN = BM, BK = 16;
+  r.bm = BM; r.bn = BN;
+  r.descs = n;
+  r.transA = descs[0].transA != 0; r.transB = descs[0].transB != 0;
+  r.pad_bytes = use_big ? env.pad_bytes : 0;
+  int total = 0;
+  bool full = p.full != 0;
+  for (int i = 0; i < n; ++i) {
+    const GemmDesc& g = descs[i];
+    full = full && g.m % BM == 0 && g.n % BN == 0 && g.k > 0 && g.k % BK == 0 && (g.lda | g.ldb) % 2 == 0 &&
+           ((uintptr_t)g.A | (uintptr_t)g.B) % 16 == 0;
+    total += ((g.m + BM - 1) / BM) * ((g.n + BN - 1) / BN);
+  }
+  r.total_tiles = r.main_tiles = r.grid = total;
+  r.ksplit = 1;
+  const int slots = env.slots;
+  if (use_big && p.splitk != 0 && total > slots) {
+    // the last partial round of workgroups: split its tiles' K range so it
+    // finishes in 1/s of a tile time; needs beta == 1 (partials are added into C)
+    // and >= 256 of K per chunk (fewer flops per added byte would be bound by
+    // the chip's f64 atomic rate)
+    const int tail = total % slots;
+    int kmin = 1 << 30;
+    bool ok = tail > 0 && 2 * tail <= slots;
+    for (int i = 0; ok && i < n; ++i) {
+      ok = descs[i].beta == 1.0 && !descs[i].a_lower && !descs[i].b_upper && !descs[i].Cin && !descs[i].C2;
+      kmin = std::min(kmin, descs[i].k);
+    }
+    const int s = ok ? std::min({slots / std::max(tail, 1), kmin / 256, 8}) : 1;
+    if (s >= 2) {
+      r.main_tiles = total - tail;
+      r.ksplit = s;
+      r.grid = r.main_tiles + tail * s;
+    }
+  }
+  // atomic epilogue: every descriptor accumulates into C (beta 1, no separate Cin / C2)
+  bool epi = p.epi != 0 && full;
+  for (int i = 0; epi && i < n; ++i) epi = descs[i].beta == 1.0 && !descs[i].Cin && !descs[i].C2 && (p.epi > 0 || descs[i].k >= 1024);
+  // rotated k loop (gemm_tile ML = 1) for the full launches
+  const bool rot = full && p.mainloop == 1;
+  // its pinned body (ML = 2): no yield poll or CU claim, 32-bit per-thread operand offsets
+  bool pipe = rot && p.pipeline == 1 && !env.yield && !env.claim;
+  for (int i = 0; pipe && i < n; ++i) pipe = gemm_pipeline_fits(BM, BN, BK, descs[i].transA, descs[i].transB, descs[i].lda, descs[i].ldb) != 0;
+  r.full = full; r.epilogue = epi ? 1 : 0;
+  r.rotated = rot; r.pipelined = pipe;
+  return r;
 }
 
 // Group descriptors by (transA, transB): one grouped launch per combination
@@ -1709,14 +1355,14 @@ int gemm_chunk_plan(const int* m, const int* n, int count, int slots, int* out) 
 // A descriptor with alpha == 0 or k <= 0 references neither A nor B (BLAS): it
 // goes out as K = 0 in a launch of its own kind, C := beta C from the
 // bounds-checked kernel's epilogue, so NaN / Inf in the operands stay out of C
-// and the k loops carry no test for it. (Gated and in-place descriptors are
-// protocols of the panel solve and stay where they are.)
-void launch_gemm_batch(const GemmDesc* descs, int n, hipStream_t stream) {
-  gemm_policy_init();
+// and the k loops carry no test for it. (Gated descriptors are a protocol of
+// the panel solve and stay where they are.) `sorted` receives the descriptors
+// in launch order; a chunk without tiles launches nothing and has no record.
+static std::vector<GemmLaunch> gemm_plan(const GemmDesc* descs, int n, const GemmPlanEnv& env, std::vector<GemmDesc>& sorted) {
   std::vector<GemmDesc> g[5];
   for (int i = 0; i < n; ++i) {
     const GemmDesc& d = descs[i];
-    if ((d.alpha == 0.0 || d.k <= 0) && !d.gate && !d.inplace) {
+    if ((d.alpha == 0.0 || d.k <= 0) && !d.gate) {
       GemmDesc z = d;
       z.k = 0;
       z.transA = z.transB = 0;
@@ -1726,13 +1372,140 @@ void launch_gemm_batch(const GemmDesc* descs, int n, hipStream_t stream) {
       g[(d.transA ? 2 : 0) | (d.transB ? 1 : 0)].push_back(d);
     }
   }
-  for (auto& v : g) {
+  std::vector<GemmLaunch> plan;
+  sorted.clear();
+  for (const auto& v : g) {
     for (size_t s = 0; s < v.size();) {
-      const int c = gemm_chunk_size(v.data() + s, (int)(v.size() - s));
-      launch_gemm_chunk(v.data() + s, c, stream);
+      const GemmDesc* d = v.data() + s;
+      const int c = gemm_chunk_cut([d](int i) { return ((d[i].m + 127) / 128) * ((d[i].n + 127) / 128); }, (int)(v.size() - s), env.slots,
+                                   env.policy.chunk_fill != 0);
+      const GemmLaunchRecord r = gemm_plan_launch(d, c, env);
+      if (r.total_tiles > 0) plan.push_back({r, (int)sorted.size()});
+      sorted.insert(sorted.end(), d, d + c);
       s += (size_t)c;
     }
   }
+  return plan;
+}
+int gemm_launch_plan(const GemmDesc* descs, int n, int slots, bool one_per_cu, bool bulk_yield, int claim, GemmLaunchRecord* out) {
+  std::vector<GemmDesc> sorted;
+  const GemmPlanEnv env{gemm_policy(), std::max(1, one_per_cu ? slots / 2 : slots), one_per_cu ? kBulkPadBytes : 0, bulk_yield, claim >= 2};
+  const std::vector<GemmLaunch> plan = gemm_plan(descs, n, env, sorted);
+  for (size_t i = 0; i < plan.size(); ++i) out[i] = plan[i].rec;
+  return (int)plan.size();
+}
+
+// ---- Launch.
+// the seven kernels of one tile shape and operand mode: the checked one, and
+// the full one with each loop body (ML 0 plain, 1 rotated, 2 pinned) and epilogue
+template <int BM, int BN, int BK, int WM, int WN, bool TA, bool TB>
+static void launch_gemm_kernel(const GemmLaunchRecord& r, const GemmBatchArgs& a, hipStream_t stream) {
+  const dim3 grid(r.grid), block(WM * WN * 64);
+  const size_t pad = (size_t)r.pad_bytes;
+  const int ml = r.pipelined ? 2 : r.rotated ? 1 : 0;
+  switch (r.full ? 1 + 2 * ml + r.epilogue : 0) {
+    case 0: hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, false, 0, 0>), grid, block, pad, stream, a); break;
+    case 1: hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, 0, 0>), grid, block, pad, stream, a); break;
+    case 2: hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, 1, 0>), grid, block, pad, stream, a); break;
+    case 3: hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, 0, 1>), grid, block, pad, stream, a); break;
+    case 4: hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, 1, 1>), grid, block, pad, stream, a); break;
+    case 5: hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, 0, 2>), grid, block, pad, stream, a); break;
+    default: hipLaunchKernelGGL((dgemm_batch_kernel<BM, BN, BK, WM, WN, TA, TB, true, 1, 2>), grid, block, pad, stream, a); break;
+  }
+}
+template <int BM, int BN, int BK, int WM, int WN>
+static void launch_gemm_shape(const GemmLaunchRecord& r, const GemmBatchArgs& a, hipStream_t stream) {
+  switch ((r.transA ? 2 : 0) | (r.transB ? 1 : 0)) {
+    case 0: launch_gemm_kernel<BM, BN, BK, WM, WN, false, false>(r, a, stream); break;
+    case 1: launch_gemm_kernel<BM, BN, BK, WM, WN, false, true>(r, a, stream); break;
+    case 2: launch_gemm_kernel<BM, BN, BK, WM, WN, true, false>(r, a, stream); break;
+    default: launch_gemm_kernel<BM, BN, BK, WM, WN, true, true>(r, a, stream); break;
+  }
+}
+
+// Issues the plan: every launch is driven by its record, and the record is
+// what the launch log keeps.
+void launch_gemm_batch(const GemmDesc* descs, int n, hipStream_t stream) {
+  const GemmPlanEnv env{gemm_policy(), gemm_slots(), t_launch_pad, t_launch_yield != 0, t_launch_claim >= 2};
+  std::vector<GemmDesc> sorted;
+  for (const GemmLaunch& l : gemm_plan(descs, n, env, sorted)) {
+    const GemmLaunchRecord& r = l.rec;
+    GemmBatchArgs a;
+    a.count = r.descs;
+    a.prio = t_launch_prio;
+    a.claim = env.claim;
+    a.yield = env.yield;
+    a.total_tiles = r.total_tiles;
+    a.main_tiles = r.main_tiles;
+    a.ksplit = r.ksplit;
+    a.gate_limit = parsec::trsm_inverse_limit();
+    int total = 0;
+    for (int i = 0; i < r.descs; ++i) {
+      const GemmDesc& g = sorted[l.first + i];
+      a.d[i] = g;
+      a.tile_start[i] = total;
+      total += ((g.m + r.bm - 1) / r.bm) * ((g.n + r.bn - 1) / r.bn);
+    }
+    a.tile_start[r.descs] = total;
+    if (r.pad_bytes && env.policy.pad_debug) {
+      static bool said = false;
+      if (!said) {
+        said = true;
+        std::fprintf(stderr, "[gemm] bulk 128x128 launch with %d extra LDS bytes (one workgroup per CU)\n", r.pad_bytes);
+      }
+    }
+    if (t_gemm_log_on) t_gemm_log[t_gemm_log_count++ % kGemmLaunchLogSize] = r;
+    if (r.bm == 128) launch_gemm_shape<128, 128, 16, 2, 4>(r, a, stream);
+    else launch_gemm_shape<64, 64, 16, 2, 2>(r, a, stream);
+  }
+}
+
+// Split-K tail of the 128x128 kernel on (1) / off (0), < 0 queries; returns the previous setting.
+int gemm_splitk(int on) {
+  const int prev = gemm_policy().splitk;
+  if (on >= 0) gemm_policy().splitk = on;
+  return prev;
+}
+
+// k loop of the full register-staged GEMM launches: 0 plain, 1 rotated, < 0 queries; returns the previous setting.
+int gemm_mainloop(int mode) {
+  const int prev = gemm_policy().mainloop;
+  if (mode >= 0) gemm_policy().mainloop = mode == 0 ? 0 : 1;
+  return prev;
+}
+
+// Body of the rotated k loop (consulted only when gemm_mainloop is 1): 0 compiler-scheduled, 1 pinned, < 0 queries; returns the previous setting.
+int gemm_pipeline(int mode) {
+  const int prev = gemm_policy().pipeline;
+  if (mode >= 0) gemm_policy().pipeline = mode == 0 ? 0 : 1;
+  return prev;
+}
+
+// Round-filling launch chunks on (1) / off (0), < 0 queries; returns the previous setting.
+int gemm_chunk_fill(int on) {
+  const int prev = gemm_policy().chunk_fill;
+  if (on >= 0) gemm_policy().chunk_fill = on != 0;
+  return prev;
+}
+
+int gemm_launch_log(int on) {
+  const int prev = t_gemm_log_on;
+  if (on >= 0) t_gemm_log_on = on != 0;
+  return prev;
+}
+
+int gemm_launch_log_read(GemmLaunchRecord* out, bool reset) {
+  const unsigned have = std::min<unsigned>(t_gemm_log_count, kGemmLaunchLogSize);
+  for (unsigned i = 0; i < have; ++i) out[i] = t_gemm_log[(t_gemm_log_count - have + i) % kGemmLaunchLogSize];
+  if (reset) t_gemm_log_count = 0;
+  return (int)have;
+}
+
+// Tile-size policy of the grouped GEMM (0 = auto, 64, 128); returns the previous one.
+int gemm_tile_policy(int p) {
+  const int prev = gemm_policy().tile;
+  if (p >= 0) gemm_policy().tile = p;
+  return prev;
 }
 
 static constexpr int kTrsmRows = 16;
@@ -3316,44 +3089,10 @@ static bool trsm_substitutable(const TrsmGemmDesc& t) {
   return t.L && t.ldl > 0 && t.n <= kTrsmMaxCols && t.n % 64 == 0 && t.ldw >= t.n;
 }
 static bool trsm_gateable(const TrsmGemmDesc& t) { return trsm_substitutable(t); }
-// Per-stream row-block counters of the in-place W-GEMM (GemmDesc::inplace):
-// zero between launches (the last workgroup of each row block resets its
-// counter), so one zeroed allocation per stream serves every launch on it.
-static unsigned* trsm_row_counters(hipStream_t stream, size_t need) {
-  static std::mutex m;
-  static std::vector<std::pair<hipStream_t, std::pair<unsigned*, size_t>>> bufs;
-  std::lock_guard<std::mutex> g(m);
-  for (auto& b : bufs)
-    if (b.first == stream) {
-      if (b.second.second >= need) return b.second.first;
-      return nullptr;  // larger than the first allocation: the caller copies instead
-    }
-  const size_t cap = std::max<size_t>(need, 1 << 16);
-  void* p = nullptr;
-  if (hipMalloc(&p, cap * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  if (hipMemset(p, 0, cap * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
-  bufs.push_back({stream, {static_cast<unsigned*>(p), cap}});
-  return static_cast<unsigned*>(p);
-}
 
-// PARSEC_TRSM_INPLACE=1 (measurement, off): the W-GEMM runs in place (no B
-// copies). Correct, but 22 % slower
-// at config 2 and 8 % at config 3 (profiles/r6_trsm_inplace.txt): a block
-// waiting for the blocks to its right keeps its CU slot, and beside the bulk
-// GEMMs the critical stream has about one slot per CU. Default: every B tile
-// copied into the workspace first, W unpacked there, the GEMM reading both.
-static std::atomic<int> g_trsm_inplace_v{-1};
-static bool trsm_inplace_on() {
-  int v = g_trsm_inplace_v.load(std::memory_order_relaxed);
-  if (v < 0) {
-    v = getenv("PARSEC_TRSM_INPLACE") && atoi(getenv("PARSEC_TRSM_INPLACE")) != 0 ? 1 : 0;
-    int expected = -1;
-    if (!g_trsm_inplace_v.compare_exchange_strong(expected, v)) v = expected;
-  }
-  return v != 0;
-}
-static constexpr int kRowSlots = 64;  // row-block counters per descriptor (m / 64)
-
+// Every B tile is copied into the workspace first, W unpacked there, and the
+// GEMM reads both (running it in place measured 22 % slower at config 2:
+// profiles/r6_trsm_inplace.txt).
 void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, double* ws) {
   const int mode = parsec::trsm_inverse_mode(-1, 0.0);
   const double limit = parsec::trsm_inverse_limit();
@@ -3418,13 +3157,6 @@ void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, doubl
       slot_of.push_back(wix);
     }
   }
-  // in place (no B copies): every descriptor of a chunk gets kRowSlots counters
-  unsigned* rows = nullptr;
-  if (trsm_inplace_on() && g_trsm_tri && !via_w.empty()) {  // in place needs the triangular k bound (a block never reads columns right of it)
-    bool fits = true;
-    for (const TrsmGemmDesc& t : via_w) fits = fits && (t.m + 63) / 64 <= kRowSlots;
-    if (fits) rows = trsm_row_counters(stream, (size_t)kMaxCopyBatch * kRowSlots);
-  }
   // the GEMM reads W unpacked (lower, zeros above)
   for (WInfo& w : wi)
       if (w.packed && !w.unpack) {
@@ -3469,7 +3201,7 @@ void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, doubl
   };
   // jobs that cannot wait for a chunk's copy launch: before everything else
   while (pend_scan.size() > (size_t)kMaxScan || pend_unpack.size() > (size_t)kMaxScan ||
-         ((rows || via_w.empty()) && (!pend_scan.empty() || !pend_unpack.empty()))) {
+         (via_w.empty() && (!pend_scan.empty() || !pend_unpack.empty()))) {
     CopyBatchArgs ca;
     ca.count = 0;
     ca.prio = t_launch_prio;
@@ -3489,25 +3221,17 @@ void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, doubl
     std::vector<GemmDesc> g(cnt);
     char* p = copies;
     int maxc = 1;
-    if (!rows) add_jobs(ca, maxc);
+    add_jobs(ca, maxc);
     for (int i = 0; i < cnt; ++i) {
       const TrsmGemmDesc& t = via_w[s0 + i];
       const WInfo& w = wi[slot_of[s0 + i]];
       GemmDesc& e = g[i];
-      if (rows) {
-        // B := B W^T in place: column blocks right to left, each written after
-        // the blocks to its right (its readers) finished
-        e.A = t.B; e.lda = t.ldb;
-        e.inplace = 1;
-        e.C2 = reinterpret_cast<double*>(rows + (size_t)i * kRowSlots);
-      } else {
-        const int c = ca.count++;
-        ca.rows[c] = t.m; ca.cols[c] = t.n; ca.ld_src[c] = t.ldb; ca.ld_dst[c] = t.m;
-        ca.src[c] = t.B; ca.dst[c] = reinterpret_cast<double*>(p);
-        maxc = std::max(maxc, t.n);
-        e.A = ca.dst[c]; e.lda = t.m;
-        p += al256((size_t)t.m * t.n * sizeof(double));
-      }
+      const int c = ca.count++;
+      ca.rows[c] = t.m; ca.cols[c] = t.n; ca.ld_src[c] = t.ldb; ca.ld_dst[c] = t.m;
+      ca.src[c] = t.B; ca.dst[c] = reinterpret_cast<double*>(p);
+      maxc = std::max(maxc, t.n);
+      e.A = ca.dst[c]; e.lda = t.m;
+      p += al256((size_t)t.m * t.n * sizeof(double));
       e.B = w.Wu; e.ldb = w.ldu;  // W unpacked (lower, zeros above)
       e.C = t.B; e.ldc = t.ldb;
       e.m = t.m; e.n = t.n; e.k = t.n;
@@ -3548,13 +3272,6 @@ void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, doubl
     }
     launch_trsm_inv(subst.data(), inv.data(), (int)subst.size(), stream);
   }
-}
-
-// In-place W-GEMM on (1) / off (0) for later launches; < 0 queries. Returns the previous setting.
-int trsm_inplace(int set) {
-  const int prev = trsm_inplace_on() ? 1 : 0;
-  if (set >= 0) g_trsm_inplace_v.store(set ? 1 : 0);
-  return prev;
 }
 
 // counters: [0] estimates published by POTRF, [1] panel decisions taken on the
@@ -3609,7 +3326,7 @@ void launch_kernel_batch(KernelBatch& b, hipStream_t stream, int device_ordinal,
       kern::t_launch_claim = prev_claim;
       kern::t_launch_yield = prev_yield;
     }
-  } prio_scope(b.critical, b.one_per_cu ? 8192 : 0, b.claim_cus, b.bulk_yield);
+  } prio_scope(b.critical, b.one_per_cu ? kern::kBulkPadBytes : 0, b.claim_cus, b.bulk_yield);
   // critical-path kernels first: a POTRF's fused update, POTRF, then TRSM, then the GEMM/SYRK updates
   if (!b.pre_gemm.empty()) kern::launch_gemm_batch(b.pre_gemm.data(), (int)b.pre_gemm.size(), stream);
   for (auto& p : b.potrf) {
@@ -3766,9 +3483,8 @@ int parsec_amd_gemm_pipeline(int mode) { return parsec::kern::gemm_pipeline(mode
 int parsec_amd_dgemm_batch(const parsec::GemmDesc* descs, int n, void* stream) {
   // PARSEC_GEMM_PAD_TEST=1: launch like a DPOTRF bulk stream (padded LDS: one
   // 128x128 workgroup per CU) -- kernel benchmarks of the in-DAG regime
-  static const bool pad_test = getenv("PARSEC_GEMM_PAD_TEST") && atoi(getenv("PARSEC_GEMM_PAD_TEST")) != 0;
   const int prev = parsec::kern::t_launch_pad;
-  if (pad_test) parsec::kern::t_launch_pad = 8192;
+  if (parsec::kern::gemm_policy().pad_test) parsec::kern::t_launch_pad = parsec::kern::kBulkPadBytes;
   parsec::kern::launch_gemm_batch(descs, n, (hipStream_t)stream);
   parsec::kern::t_launch_pad = prev;
   return (int)hipGetLastError();

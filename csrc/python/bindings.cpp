@@ -109,6 +109,49 @@ static py::object dtd_arg(Task* t, int i) {
 template <class M>
 static void bind_tiled_common(py::class_<M, TiledMatrix>& c) { (void)c; }
 
+// every GemmDesc field but the gate protocol (that runs through kernel_trsm_w_batch); missing keys are 0
+static std::vector<GemmDesc> gemm_descs_from_dicts(const std::vector<py::dict>& ds, const std::string& who) {
+  static const char* const known[] = {"A", "B", "C", "m", "n", "k", "lda", "ldb", "ldc", "alpha", "beta", "transA", "transB", "lower_only", "a_lower",
+                                      "b_upper", "Cin", "ldcin", "C2", "ldc2"};
+  std::vector<GemmDesc> v;
+  for (const auto& d : ds) {
+    for (const auto& kv : d) {
+      const std::string key = py::cast<std::string>(kv.first);
+      bool ok = false;
+      for (const char* k : known) ok = ok || key == k;
+      if (!ok) throw std::invalid_argument(who + ": unknown descriptor key '" + key + "'");
+    }
+    auto ptr = [&](const char* k) { return d.contains(k) ? d[k].cast<uintptr_t>() : (uintptr_t)0; };
+    auto num = [&](const char* k) { return d.contains(k) ? d[k].cast<int>() : 0; };
+    auto real = [&](const char* k) { return d.contains(k) ? d[k].cast<double>() : 0.0; };
+    GemmDesc g{};
+    g.A = (const double*)ptr("A"); g.B = (const double*)ptr("B"); g.C = (double*)ptr("C");
+    g.m = num("m"); g.n = num("n"); g.k = num("k");
+    g.lda = num("lda"); g.ldb = num("ldb"); g.ldc = num("ldc");
+    g.alpha = real("alpha"); g.beta = real("beta");
+    g.transA = num("transA") ? 1 : 0; g.transB = num("transB") ? 1 : 0;
+    g.lower_only = num("lower_only") ? 1 : 0; g.a_lower = num("a_lower") ? 1 : 0; g.b_upper = num("b_upper") ? 1 : 0;
+    g.Cin = (const double*)ptr("Cin"); g.ldcin = num("ldcin");
+    g.C2 = (double*)ptr("C2"); g.ldc2 = num("ldc2");
+    v.push_back(g);
+  }
+  return v;
+}
+
+static py::dict gemm_record_dict(const kern::GemmLaunchRecord& r) {
+  py::dict e;
+  e["BM"] = r.bm; e["BN"] = r.bn;
+  e["transA"] = (int)r.transA; e["transB"] = (int)r.transB;
+  e["descs"] = r.descs;
+  e["total_tiles"] = r.total_tiles; e["main_tiles"] = r.main_tiles; e["ksplit"] = r.ksplit;
+  e["grid"] = r.grid;
+  e["full"] = (bool)r.full; e["epilogue"] = (int)r.epilogue;
+  e["rotated"] = (bool)r.rotated;
+  e["pipelined"] = (bool)r.pipelined;
+  e["pad_bytes"] = r.pad_bytes;
+  return e;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(_C, m) {
@@ -506,8 +549,6 @@ PYBIND11_MODULE(_C, m) {
         tp->destructor_hook = [info]() { delete info; };
         return py::make_tuple(py::cast(tp, py::return_value_policy::take_ownership), (uintptr_t)info);
       });
-  m.def("trsm_inplace", [](int set) { return kern::trsm_inplace(set); }, py::arg("set") = -1,
-        "Panel-solve W-GEMM in place (no B-tile copies; PARSEC_TRSM_INPLACE): 1 on, 0 off, < 0 query; returns the previous setting");
   m.def("dpotrf_fuse_syrk", [](int set) { return algos::dpotrf_fuse_syrk(set); }, py::arg("set") = -1,
         "SYRK(k-1,k) fused into POTRF(k) for new dpotrf_L.jdf taskpools (PARSEC_DPOTRF_FUSE_SYRK); returns the previous value");
   m.def("dpotrf_jdf_new", [](TiledMatrix* A) {
@@ -770,32 +811,8 @@ PYBIND11_MODULE(_C, m) {
     }
     return parsec_amd_dgemm_batch(v.data(), (int)v.size(), (void*)stream);
   });
-  // every GemmDesc field but the gate / inplace protocols (those run through kernel_trsm_w_batch); missing keys are 0
   m.def("kernel_dgemm_batch_ex", [](const std::vector<py::dict>& ds, uintptr_t stream, bool bulk_yield) {
-    static const char* const known[] = {"A", "B", "C", "m", "n", "k", "lda", "ldb", "ldc", "alpha", "beta", "transA", "transB", "lower_only", "a_lower",
-                                        "b_upper", "Cin", "ldcin", "C2", "ldc2"};
-    std::vector<GemmDesc> v;
-    for (const auto& d : ds) {
-      for (const auto& kv : d) {
-        const std::string key = py::cast<std::string>(kv.first);
-        bool ok = false;
-        for (const char* k : known) ok = ok || key == k;
-        if (!ok) throw std::invalid_argument("kernel_dgemm_batch_ex: unknown descriptor key '" + key + "'");
-      }
-      auto ptr = [&](const char* k) { return d.contains(k) ? d[k].cast<uintptr_t>() : (uintptr_t)0; };
-      auto num = [&](const char* k) { return d.contains(k) ? d[k].cast<int>() : 0; };
-      auto real = [&](const char* k) { return d.contains(k) ? d[k].cast<double>() : 0.0; };
-      GemmDesc g{};
-      g.A = (const double*)ptr("A"); g.B = (const double*)ptr("B"); g.C = (double*)ptr("C");
-      g.m = num("m"); g.n = num("n"); g.k = num("k");
-      g.lda = num("lda"); g.ldb = num("ldb"); g.ldc = num("ldc");
-      g.alpha = real("alpha"); g.beta = real("beta");
-      g.transA = num("transA") ? 1 : 0; g.transB = num("transB") ? 1 : 0;
-      g.lower_only = num("lower_only") ? 1 : 0; g.a_lower = num("a_lower") ? 1 : 0; g.b_upper = num("b_upper") ? 1 : 0;
-      g.Cin = (const double*)ptr("Cin"); g.ldcin = num("ldcin");
-      g.C2 = (double*)ptr("C2"); g.ldc2 = num("ldc2");
-      v.push_back(g);
-    }
+    const std::vector<GemmDesc> v = gemm_descs_from_dicts(ds, "kernel_dgemm_batch_ex");
     if (bulk_yield) return parsec_amd_dgemm_batch_yield(v.data(), (int)v.size(), (void*)stream);
     return parsec_amd_dgemm_batch(v.data(), (int)v.size(), (void*)stream);
   }, py::arg("descs"), py::arg("stream") = 0, py::arg("bulk_yield") = false,
@@ -811,23 +828,20 @@ PYBIND11_MODULE(_C, m) {
     const int cnt = kern::gemm_launch_log_read(recs, reset);
     if (!enable.is_none()) kern::gemm_launch_log(enable.cast<bool>() ? 1 : 0);
     py::list out;
-    for (int i = 0; i < cnt; ++i) {
-      const kern::GemmLaunchRecord& r = recs[i];
-      py::dict e;
-      e["BM"] = r.bm; e["BN"] = r.bn;
-      e["transA"] = (int)r.transA; e["transB"] = (int)r.transB;
-      e["descs"] = r.descs;
-      e["total_tiles"] = r.total_tiles; e["main_tiles"] = r.main_tiles; e["ksplit"] = r.ksplit;
-      e["grid"] = r.grid;
-      e["full"] = (bool)r.full; e["epilogue"] = (int)r.epilogue;
-      e["rotated"] = (bool)r.rotated; e["direct_lds"] = (bool)r.direct_lds; e["persistent"] = (bool)r.persistent; e["ordered"] = (bool)r.ordered;
-      e["pipelined"] = (bool)r.pipelined;
-      e["pad_bytes"] = r.pad_bytes;
-      out.append(e);
-    }
+    for (int i = 0; i < cnt; ++i) out.append(gemm_record_dict(recs[i]));
     return out;
   }, py::arg("enable") = py::none(), py::arg("reset") = false,
      "grouped-DGEMM launches the calling thread recorded (oldest first, the last 64): a dict per launch; reset empties the record, enable switches recording on / off");
+  m.def("kernel_gemm_launch_plan", [](const std::vector<py::dict>& ds, int slots, bool one_per_cu, bool bulk_yield, int claim) {
+    const std::vector<GemmDesc> v = gemm_descs_from_dicts(ds, "kernel_gemm_launch_plan");
+    std::vector<kern::GemmLaunchRecord> recs(v.size());
+    recs.resize((size_t)kern::gemm_launch_plan(v.data(), (int)v.size(), slots, one_per_cu, bulk_yield, claim, recs.data()));
+    py::list out;
+    for (const auto& r : recs) out.append(gemm_record_dict(r));
+    return out;
+  }, py::arg("descs"), py::arg("slots"), py::arg("one_per_cu") = false, py::arg("bulk_yield") = false, py::arg("claim") = 0,
+     "the launches kernel_dgemm_batch_ex would issue for these descriptor dicts on `slots` resident 128x128 workgroups (a dict per launch, as kernel_gemm_launch_log gives); "
+     "one_per_cu: a padded bulk launch, bulk_yield / claim (>= 2): a yielding bulk / claiming critical stream. Host code only: no device, pointers are never dereferenced");
   m.def("kernel_gemm_chunk_fill", [](int on) { return kern::gemm_chunk_fill(on); }, "round-filling launch chunks of the grouped DGEMM: 1 on, 0 off (fixed launches of 40 descriptors), -1 query; returns the previous setting");
   m.def("kernel_gemm_chunk_plan", [](const std::vector<std::pair<int, int>>& shapes, int slots) {
     std::vector<int> mm, nn, out(shapes.size());

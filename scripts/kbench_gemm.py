@@ -1,6 +1,9 @@
-"""Grouped fp64 GEMM throughput for one kernel variant (PARSEC_GEMM_VARIANT /
-PARSEC_GEMM_FULL are read once per process): the DPOTRF trailing-update shape
-(C -= A B^T on nb x nb tiles) and one large square GEMM.
+"""Grouped fp64 GEMM throughput: the DPOTRF trailing-update shape (C -= A B^T on
+nb x nb tiles) and one large square GEMM. PARSEC_GEMM_FULL=0 (read once per
+process) times the bounds-checked kernel, PARSEC_GEMM_PAD_TEST=1 the padded
+one-workgroup-per-CU launch of a DPOTRF bulk stream. (The kernel variants
+PARSEC_GEMM_VARIANT once selected are gone; d5f2999 is the last commit that
+has them.)
 
 --ab: the three k loops (plain = pa.kernel_gemm_mainloop 0; rotated with the
 compiler-scheduled body = mainloop 1, pa.kernel_gemm_pipeline 0; rotated with the
@@ -65,7 +68,7 @@ def main():
     dev = torch.device("cuda", 0)
     s = torch.cuda.current_stream().cuda_stream
     do_ab = "--ab" in sys.argv[1:]
-    tag = f"variant={os.environ.get('PARSEC_GEMM_VARIANT', '0')} full={os.environ.get('PARSEC_GEMM_FULL', '1')} pad={os.environ.get('PARSEC_GEMM_PAD_TEST', '0')}"
+    tag = f"full={os.environ.get('PARSEC_GEMM_FULL', '1')} pad={os.environ.get('PARSEC_GEMM_PAD_TEST', '0')}"
     prev, prev_pipe = pa.kernel_gemm_mainloop(-1), pa.kernel_gemm_pipeline(-1)
     all_equal = True
     for nb, ntask in ((512, 32), (1024, 16), (1024, 40)):
