@@ -24,6 +24,12 @@
            ||L U - A||_F / ||A||_F; the same process then times
            torch.linalg.lu_factor / lu_solve on the dense data -- torch PIVOTS
            (partial pivoting), so the yardstick does more work than we do
+  potri    the inverse with the Cholesky factor of a seeded SPD matrix: DTRTRI
+           (N^3 / 3) and DPOTRI (2/3 N^3) on the dense factor torch computed,
+           DPOINV (N^3) on the matrix, A restored every timed step; the same
+           process then times torch.cholesky_inverse on that factor, and
+           ||A X - I||_F / (||A||_F ||X||_F) is printed for ours and torch's.
+           --cond C swaps in a matrix of condition number C
 
 Multi-GPU: launch like bench.py (torch.distributed.run, one rank per GPU).
 
@@ -33,9 +39,11 @@ Multi-GPU: launch like bench.py (torch.distributed.run, one rank per GPU).
     python benchmarks/bench_workloads.py potrs --n 16384 --nb 512 --nrhs 16384
     python benchmarks/bench_workloads.py gels --m 32768 --n 8192 --nb 512 --nrhs 512
     python benchmarks/bench_workloads.py getrf --n 16384 --nb 512 --nrhs 512
+    python benchmarks/bench_workloads.py potri --n 16384 --nb 512
 """
 import argparse
 import json
+import math
 import os
 import sys
 import time
@@ -608,15 +616,160 @@ def bench_getrf(args):
     return out, 0
 
 
+def bench_potri(args):
+    import torch
+
+    import parsec_amd as pa
+
+    world, rank, local = _dist()
+    if world > 1:
+        raise RuntimeError("potri: one GPU (the yardstick is a single-device torch.cholesky_inverse)")
+    if not torch.cuda.is_available():
+        raise RuntimeError("potri: no GPU")
+    N, nb = args.n, args.nb
+    dev = torch.device("cuda", 0)
+    ctx = pa.init(args.cores)
+    gpu = pa.first_gpu_device_index()
+    if gpu < 0:
+        raise RuntimeError("no GPU device registered in the runtime")
+    NT = -(-N // nb)
+
+    def run(tp):
+        ctx.add_taskpool(tp)
+        ctx.start()
+        ctx.wait()
+
+    def tiled(dense):  # the store image [n][m][col][row] of a dense N x N matrix
+        pad = torch.zeros((NT * nb, NT * nb), dtype=torch.float64, device=dev)
+        pad[:N, :N] = dense
+        return pad.reshape(NT, nb, NT, nb).permute(2, 0, 3, 1).contiguous()
+
+    def lower_of(store):  # a dense COPY of the lower triangle of a tiled store
+        return torch.tril(store.permute(1, 3, 0, 2).reshape(NT * nb, NT * nb)[:N, :N])
+
+    gen = torch.Generator(device=dev).manual_seed(12345)
+    if args.cond > 1.0:
+        # Q diag(logspace(0, -log10(cond))) Q^T: a prescribed condition number
+        Q, _ = torch.linalg.qr(torch.randn((N, N), dtype=torch.float64, device=dev, generator=gen))
+        d = torch.logspace(0.0, -math.log10(args.cond), N, dtype=torch.float64, device=dev)
+        S = (Q * d) @ Q.t()
+        S = (S + S.t()) / 2
+        del Q
+    else:
+        # (R + R^T) / 2 + N I, R uniform: the well-conditioned family of the tests
+        S = torch.rand((N, N), dtype=torch.float64, device=dev, generator=gen)
+        S = (S + S.t()) / 2 + N * torch.eye(N, dtype=torch.float64, device=dev)
+    Lf = torch.linalg.cholesky(S)  # the dense factor: our input and torch's
+    backupS = tiled(S)
+    backupL = tiled(Lf)
+    sa = backupL.clone()
+    A = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nb, N, N, device=gpu, ptr=sa.data_ptr())
+    torch.cuda.synchronize()
+    infos = []
+
+    def step_trtri():
+        sa.copy_(backupL)
+        torch.cuda.synchronize()
+        tp, info = pa.dtrtri_new(pa.MATRIX_LOWER, pa.MATRIX_NONUNIT, A)
+        run(tp)
+        infos.append(pa.read_int(info))
+
+    def step_potri():
+        sa.copy_(backupL)
+        torch.cuda.synchronize()
+        tp = pa.dpotri_new(pa.MATRIX_LOWER, A)
+        run(tp)
+        pa.taskpool_free(tp)
+
+    def step_poinv():
+        sa.copy_(backupS)
+        torch.cuda.synchronize()
+        tp, info = pa.dpoinv_new(pa.MATRIX_LOWER, A)
+        run(tp)
+        infos.append(pa.read_int(info))
+        pa.taskpool_free(tp)
+
+    def timed(step):
+        for _ in range(args.warmup):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps
+
+    eye = torch.eye(N, dtype=torch.float64, device=dev)
+    nS, nL = torch.linalg.norm(S), torch.linalg.norm(Lf)
+
+    def tri_residual(X):  # ||X L - I||_F / (||X||_F ||L||_F)
+        return float(torch.linalg.norm(X @ Lf - eye) / (torch.linalg.norm(X) * nL))
+
+    def inv_residual(X):  # ||A X - I||_F / (||A||_F ||X||_F)
+        return float(torch.linalg.norm(S @ X - eye) / (nS * torch.linalg.norm(X)))
+
+    def sym(T):
+        return T + torch.tril(T, -1).t()
+
+    dt_trtri = timed(step_trtri)
+    res_trtri = tri_residual(lower_of(sa))
+    dt_potri = timed(step_potri)
+    res_potri = inv_residual(sym(lower_of(sa)))
+    dt_poinv = timed(step_poinv)
+    res_poinv = inv_residual(sym(lower_of(sa)))
+    if any(infos):
+        raise RuntimeError(f"a zero diagonal entry / a failed factorization was reported: info {infos}")
+    del sa, backupS, backupL
+    # yardsticks on the dense factor, same process (out of place, no restore needed)
+    for _ in range(max(1, args.warmup)):
+        Y = torch.cholesky_inverse(Lf)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        Y = torch.cholesky_inverse(Lf)
+    torch.cuda.synchronize()
+    dty_potri = (time.perf_counter() - t0) / args.steps
+    res_y_potri = inv_residual(Y)
+    del Y
+    for _ in range(max(1, args.warmup)):
+        Y = torch.linalg.solve_triangular(Lf, eye, upper=False)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        Y = torch.linalg.solve_triangular(Lf, eye, upper=False)
+    torch.cuda.synchronize()
+    dty_trtri = (time.perf_counter() - t0) / args.steps
+    res_y_trtri = tri_residual(Y)
+    ctx.fini()
+    f_trtri, f_potri, f_poinv = N ** 3 / 3.0, 2.0 * N ** 3 / 3.0, float(N) ** 3
+    print(f"residual ||A X - I||_F / (||A||_F ||X||_F): DPOTRI {res_potri:.3e}, DPOINV {res_poinv:.3e}, torch.cholesky_inverse {res_y_potri:.3e}; "
+          f"||X L - I||_F / (||X||_F ||L||_F): DTRTRI {res_trtri:.3e}, torch.linalg.solve_triangular {res_y_trtri:.3e}", flush=True)
+    out = {"metric": "GFLOP/s DPOTRI (dtrtri_L.jdf + dlauum_L.jdf on the dense factor, HBM-resident tiles, A restored every step)",
+           "value": round(f_potri / dt_potri / 1e9, 1), "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(dt_potri * 1e3, 3), "higher_is_better": True, "dtype": "fp64",
+           "flops_dtrtri": f_trtri, "flops_dpotri": f_potri, "flops_dpoinv": f_poinv,
+           "dtrtri_gflops": round(f_trtri / dt_trtri / 1e9, 1), "dtrtri_ms": round(dt_trtri * 1e3, 3), "dtrtri_residual": res_trtri,
+           "dpotri_residual": res_potri,
+           "dpoinv_gflops": round(f_poinv / dt_poinv / 1e9, 1), "dpoinv_ms": round(dt_poinv * 1e3, 3), "dpoinv_residual": res_poinv,
+           "yardstick": "torch.cholesky_inverse (and torch.linalg.solve_triangular against I for DTRTRI) on the dense factor, same process",
+           "yardstick_potri_gflops": round(f_potri / dty_potri / 1e9, 1), "yardstick_potri_ms": round(dty_potri * 1e3, 3), "yardstick_potri_residual": res_y_potri,
+           "yardstick_trtri_ms": round(dty_trtri * 1e3, 3), "yardstick_trtri_residual": res_y_trtri,
+           "ratio_to_yardstick": round(dty_potri / dt_potri, 3), "dtrtri_ratio_to_yardstick": round(dty_trtri / dt_trtri, 3),
+           "dpotri_residual_ratio": round(res_potri / res_y_potri, 2), "dtrtri_residual_ratio": round(res_trtri / res_y_trtri, 2),
+           "config": {"model": "DPOTRI", "N": N, "nb": nb, "cond": args.cond, "cores": args.cores}}
+    return out, 0
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm", "potrs", "gels", "getrf"])
+    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm", "potrs", "gels", "getrf", "potri"])
     ap.add_argument("--n", "--size", dest="n", type=int, default=None, help="matrix order (use --size under torchrun)")
     ap.add_argument("--m", type=int, default=None, help="gels: rows of A (default: n)")
     ap.add_argument("--nb", type=int, default=512)
     ap.add_argument("--ib", type=int, default=32, help="qr: accepted for the reference's command line; both taskpools factor 32-column sub-panels (qr_sub2c) and apply one nb x nb block reflector per tile")
     ap.add_argument("--nrhs", type=int, default=None, help="potrs / gels / getrf: right-hand sides (default: n)")
     ap.add_argument("--nbr", type=int, default=0, help="potrs / gels / getrf: tile width of B (default: min(nb, nrhs))")
+    ap.add_argument("--cond", type=float, default=0.0, help="potri: condition number of the matrix, Q diag(logspace) Q^T (default 0: the well-conditioned (R + R^T) / 2 + N I)")
     ap.add_argument("--b", type=int, default=128)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--steps", type=int, default=2)
@@ -631,12 +784,12 @@ def main():
                     help="qr: rows per TS domain of the hierarchical tree (0: one flat TS chain per process row, TT binary tree across process rows; 1 GPU measured fastest flat: profiles/r3_qr_tree_ab.jsonl)")
     args = ap.parse_args()
     if args.n is None:
-        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048, "potrs": 16384, "gels": 16384, "getrf": 16384}[args.workload]
+        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048, "potrs": 16384, "gels": 16384, "getrf": 16384, "potri": 16384}[args.workload]
     if args.nrhs is None:
         args.nrhs = args.n
     if args.m is None:
         args.m = args.n
-    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm, "potrs": bench_potrs, "gels": bench_gels, "getrf": bench_getrf}[args.workload]
+    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm, "potrs": bench_potrs, "gels": bench_gels, "getrf": bench_getrf, "potri": bench_potri}[args.workload]
     out, rank = fn(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

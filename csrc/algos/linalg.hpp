@@ -32,6 +32,27 @@ Taskpool* dpotrs_new(int uplo, TiledMatrix* A, TiledMatrix* B);
 // untouched. One rank only (nullptr otherwise): ranks see only the pivots of
 // their own diagonal tiles.
 Taskpool* dposv_new(int uplo, TiledMatrix* A, TiledMatrix* B, int* info);
+// Tiled inverse of a lower triangular matrix, A := L^-1 in place, from the JDF
+// source algos/jdf/dtrtri_L.jdf: uplo Lower, diag NonUnit, A square (M == N)
+// with square tiles, double; a ragged last tile is allowed. Only A's lower tiles
+// and the lower triangles of its diagonal tiles are read and written.
+// `info_host` (optional) receives the 1-based global index of the first diagonal
+// entry that is exactly zero (0 = none). Anything else returns nullptr after a
+// warning.
+ptg::PtgTaskpool* dtrtri_new(int uplo, int diag, TiledMatrix* A, int* info_host);
+// A := lower(L^T L) in place from the JDF source algos/jdf/dlauum_L.jdf, L the
+// lower triangle of A; the same arguments and the same footprint as dtrtri_new.
+ptg::PtgTaskpool* dlauum_new(int uplo, TiledMatrix* A);
+// The inverse of an SPD matrix from the Cholesky factor L that dpotrf left in A
+// (lower only): dtrtri_new composed with dlauum_new, A := L^-T L^-1. Only the
+// lower triangle of the inverse is written (the caller symmetrises it if
+// needed). Freeing the returned taskpool (taskpool_free) frees the two parts.
+Taskpool* dpotri_new(int uplo, TiledMatrix* A);
+// dpotrf_jdf_new composed with dpotri_new. When the factorization fails (*info
+// != 0 once it completed) the inverse taskpools start empty: A holds what
+// DPOTRF left. `info` is required. One rank only (nullptr otherwise): ranks see
+// only the pivots of their own diagonal tiles.
+Taskpool* dpoinv_new(int uplo, TiledMatrix* A, int* info);
 // Tiled LU factorization WITHOUT pivoting, A = L U, from the JDF source
 // algos/jdf/dgetrf_nopiv.jdf: A is square (M == N) with square tiles, double; a
 // ragged last tile is allowed. On return A holds L (unit lower, its diagonal not

@@ -1146,6 +1146,14 @@ parsec_taskpool_t* parsec_dgetrs_nopiv_New(parsec_matrix_trans_t trans, parsec_t
 parsec_taskpool_t* parsec_dgesv_nopiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info) {
   return algos::dgesv_nopiv_new(tm_of(A), tm_of(B), info);
 }
+parsec_taskpool_t* parsec_dtrtri_New(parsec_matrix_uplo_t uplo, parsec_matrix_diag_t diag, parsec_tiled_matrix_t* A, int* info) {
+  return algos::dtrtri_new((int)uplo, (int)diag, tm_of(A), info);
+}
+parsec_taskpool_t* parsec_dlauum_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A) { return algos::dlauum_new((int)uplo, tm_of(A)); }
+parsec_taskpool_t* parsec_dpotri_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A) { return algos::dpotri_new((int)uplo, tm_of(A)); }
+parsec_taskpool_t* parsec_dpoinv_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, int* info) {
+  return algos::dpoinv_new((int)uplo, tm_of(A), info);
+}
 int parsec_apply(parsec_context_t* parsec, parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_unary_op_t operation, void* op_args) {
   parsec_taskpool_t* tp = parsec_apply_New(uplo, A, operation, op_args);
   parsec_context_add_taskpool(parsec, tp);

@@ -553,7 +553,9 @@ int context_add_taskpool(Context* ctx, Taskpool* tp) {
   if (ptg_to_dtd_enabled()) ptg_to_dtd_taskpool_init(ctx, tp);
   if (!ready.empty()) {
     ExecutionStream* es = my_execution_stream();
-    if (!es || es->ctx != ctx) es = ctx->all_es[0];
+    // a manager (GPU, communication) has no scheduler queue of its own: a child of
+    // a composed taskpool that it starts goes to a compute thread's queues
+    if (!es || es->ctx != ctx || es->is_manager) es = ctx->all_es[0];
     // startup tasks are distributed over the compute threads round-robin
     int nes = (int)ctx->all_es.size();
     if (nes > 1 && ready.size() > 1) {

@@ -175,6 +175,44 @@ struct GetrfDesc {
   int info_base = 0;  // added to the index reported (the tile's first row in the matrix)
 };
 
+// Inverse of an n x n lower triangular tile, non-unit diagonal (1 <= n <= 1152,
+// lda >= n): A := L^-1 in place, or W_out (ld ldw) := L^-1 with A left intact.
+// Only the lower triangle is read and only the lower triangle of the target is
+// written; rows n .. ld-1 are never touched. *info (optional) receives info_base
+// + the 1-based index of the first diagonal entry that is exactly zero (the
+// smallest index wins, the word is left alone otherwise); the kernel still
+// finishes and the tile then holds inf / nan.
+struct TrtriDesc {
+  double* A;
+  int n, lda;
+  int* info = nullptr;  // device pointer (may be null)
+  int info_base = 0;
+  double* W_out = nullptr;
+  int ldw = 0;
+  // optional: the inverses of L's 64 x 64 diagonal blocks (dtrtri_diag_kernel's layout)
+  const double* invD = nullptr;
+};
+
+// B := alpha L^T B in place; L is n x n lower (its strict upper triangle is
+// never read), B is n x nrhs. With `lower`, B is itself n x n lower triangular:
+// its strict upper triangle is neither read nor written (the LAUUM product).
+struct TrmmDesc {
+  const double* L;
+  double* B;
+  int n, nrhs;
+  int ldl, ldb;
+  double alpha;
+  uint8_t lower = 0;
+};
+static_assert(sizeof(TrmmDesc) == 48, "TrmmDesc grew: the TRMM kernel argument block is sized for 64 of them");
+
+// A := lower(L^T L) in place for an n x n lower triangular tile (lda >= n); the
+// strict upper triangle and rows n .. lda-1 are never touched.
+struct LauumDesc {
+  double* A;
+  int n, lda;
+};
+
 // Panel solve through the explicit inverse: B := B * W^T with W = L^-1 from
 // POTRF (one grouped MFMA GEMM instead of a sequential blocked solve per tile).
 struct TrsmGemmDesc {
@@ -207,6 +245,12 @@ void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipS
 // tile LU without pivoting; ws: getrf_workspace_bytes(g)
 void launch_getrf_nopiv(const GetrfDesc& g, hipStream_t stream, double* ws);
 size_t getrf_workspace_bytes(const GetrfDesc& g);
+// tile TRTRI / grouped TRMM (B := alpha L^T B) / tile LAUUM; ws: *_workspace_bytes
+void launch_trtri(const TrtriDesc& t, hipStream_t stream, double* ws);
+size_t trtri_workspace_bytes(const TrtriDesc& t);
+void launch_trmm_lt_batch(const TrmmDesc* descs, int n, hipStream_t stream);
+void launch_lauum(const LauumDesc& l, hipStream_t stream, double* ws);
+size_t lauum_workspace_bytes(const LauumDesc& l);
 // Vout (rows x min(rows, cols), ld rows) := the unit-lower V stored below the
 // diagonal of a factored QR diagonal tile A (ld lda): ones on the diagonal,
 // zeros above (the layout of QrPanelDesc::Vcopy)
@@ -333,6 +377,9 @@ struct KernelBatch {
   std::vector<TrsmLeftDesc> trsm_left;
   std::vector<PotrfDesc> potrf;
   std::vector<GetrfDesc> getrf;
+  std::vector<TrtriDesc> trtri;
+  std::vector<TrmmDesc> trmm;
+  std::vector<LauumDesc> lauum;
   std::vector<TrsmGemmDesc> trsm_w;
   std::vector<StencilDesc> stencil;
   std::vector<QrPanelDesc> qr_panel;
@@ -345,8 +392,8 @@ struct KernelBatch {
   // (kernels: g_crit_cu, bulk_yield) so the chain runs at idle speed
   int claim_cus = 0;  // 1: tile-POTRF steps claim, 2: every kernel of the launch
   bool bulk_yield = false;  // bulk launch: poll the claims
-  bool empty() const { return pre_gemm.empty() && gemm.empty() && trsm.empty() && trsm_left.empty() && potrf.empty() && getrf.empty() && trsm_w.empty() && stencil.empty() && qr_panel.empty() && qr_apply.empty() && generic.empty(); }
-  void clear() { pre_gemm.clear(); gemm.clear(); trsm.clear(); trsm_left.clear(); potrf.clear(); getrf.clear(); trsm_w.clear(); stencil.clear(); qr_panel.clear(); qr_apply.clear(); generic.clear(); }
+  bool empty() const { return pre_gemm.empty() && gemm.empty() && trsm.empty() && trsm_left.empty() && potrf.empty() && getrf.empty() && trtri.empty() && trmm.empty() && lauum.empty() && trsm_w.empty() && stencil.empty() && qr_panel.empty() && qr_apply.empty() && generic.empty(); }
+  void clear() { pre_gemm.clear(); gemm.clear(); trsm.clear(); trsm_left.clear(); potrf.clear(); getrf.clear(); trtri.clear(); trmm.clear(); lauum.clear(); trsm_w.clear(); stencil.clear(); qr_panel.clear(); qr_apply.clear(); generic.clear(); }
 };
 
 struct HipDevice;

@@ -1133,7 +1133,7 @@ static size_t batch_tiles(const KernelBatch& b) {
   size_t t = 0;
   for (const GemmDesc& g : b.gemm) t += (size_t)((g.m + 127) / 128) * ((g.n + 127) / 128);
   for (const QrApplyDesc& q : b.qr_apply) t += (size_t)((q.m2 + 127) / 128) * ((q.n + 127) / 128);
-  return t + 16 * (b.trsm.size() + b.trsm_left.size() + b.trsm_w.size() + b.stencil.size());
+  return t + 16 * (b.trsm.size() + b.trsm_left.size() + b.trmm.size() + b.trsm_w.size() + b.stencil.size());
 }
 
 // ------------------------------------------------------------- execution

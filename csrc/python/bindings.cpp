@@ -36,6 +36,9 @@ extern "C" int parsec_amd_potrf_stamps(long long* out);
 extern "C" int parsec_amd_dtrsm_batch(const TrsmDesc* descs, int n, void* stream);
 extern "C" int parsec_amd_dtrsm_left_batch(const TrsmLeftDesc* descs, int n, void* stream);
 extern "C" int parsec_amd_dgetrf_nopiv_tile(double* A, int n, int lda, int* info, double* invL, double* invU, void* stream);
+extern "C" int parsec_amd_dtrtri_tile(double* A, int n, int lda, int* info, int info_base, double* W, int ldw, void* stream);
+extern "C" int parsec_amd_dtrmm_lt_batch(const parsec::TrmmDesc* descs, int n, void* stream);
+extern "C" int parsec_amd_dlauum_tile(double* A, int n, int lda, void* stream);
 extern "C" int parsec_amd_dpotrf_tile(double* A, int n, int lda, int* info, void* stream);
 extern "C" int parsec_amd_trsm_w_batch(const parsec::TrsmGemmDesc* d, int n, void* stream);
 extern "C" int parsec_amd_dpotrf_tile_w(double* A, int n, int lda, int* info, double* W, int ldw, void* stream, int pack);
@@ -591,6 +594,37 @@ PYBIND11_MODULE(_C, m) {
       }, py::arg("A"),
       "tiled LU WITHOUT pivoting (square A, square tiles) from the ptgpp-compiled dgetrf_nopiv.jdf: A := L\\U, L unit lower; returns (taskpool, info address) or "
       "None. info is the 1-based index of the first pivot that is exactly zero; the matrix must not need pivoting");
+  m.def("dtrtri_new", [](int uplo, int diag, TiledMatrix* A) -> py::object {
+        auto* info = new int(0);
+        auto* tp = algos::dtrtri_new(uplo, diag, A, info);
+        if (!tp) {
+          delete info;
+          return py::none();
+        }
+        auto prev = tp->destructor_hook;
+        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
+        return py::make_tuple(py::cast(tp, py::return_value_policy::take_ownership), (uintptr_t)info);
+      }, py::arg("uplo"), py::arg("diag"), py::arg("A"),
+      "tiled inverse of a lower triangular matrix in place (MATRIX_LOWER, MATRIX_NONUNIT; square A, square tiles) from the ptgpp-compiled dtrtri_L.jdf; returns "
+      "(taskpool, info address) or None. info is the 1-based index of the first diagonal entry that is exactly zero. Only the lower tiles / triangles are touched");
+  m.def("dlauum_new", [](int uplo, TiledMatrix* A) { return algos::dlauum_new(uplo, A); }, py::arg("uplo"), py::arg("A"),
+        py::return_value_policy::take_ownership, "A := lower(L^T L) in place (MATRIX_LOWER) from the ptgpp-compiled dlauum_L.jdf; None for anything else");
+  m.def("dpotri_new", [](int uplo, TiledMatrix* A) { return algos::dpotri_new(uplo, A); }, py::arg("uplo"), py::arg("A"),
+        py::return_value_policy::reference,
+        "the inverse from the Cholesky factor in A (lower): dtrtri then dlauum, the lower triangle of A := A^-1; None on invalid arguments. Release with taskpool_free");
+  m.def("dpoinv_new", [](int uplo, TiledMatrix* A) -> py::object {
+        auto* info = new int(0);
+        Taskpool* tp = algos::dpoinv_new(uplo, A, info);
+        if (!tp) {
+          delete info;
+          return py::none();
+        }
+        auto prev = tp->destructor_hook;
+        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
+        return py::make_tuple(py::cast(tp, py::return_value_policy::reference), (uintptr_t)info);
+      }, py::arg("uplo"), py::arg("A"),
+      "Cholesky factorization then inverse (lower, one rank); returns (taskpool, info address) or None. When info != 0 the inverse does not run and A holds what "
+      "the factorization left");
   m.def("dgetrs_nopiv_new", [](int trans, TiledMatrix* A, TiledMatrix* B) { return algos::dgetrs_nopiv_new(trans, A, B); }, py::arg("trans"), py::arg("A"),
         py::arg("B"), py::return_value_policy::reference,
         "solve op(A) X = B with the factor of dgetrf_nopiv_new in A (MATRIX_NOTRANS or MATRIX_TRANS); B.mb must equal A.nb; None on invalid arguments. Release "
@@ -890,6 +924,29 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("A"), py::arg("n"), py::arg("lda"), py::arg("info") = 0, py::arg("invL") = 0, py::arg("invU") = 0, py::arg("stream") = 0,
      "tile LU without pivoting on the GPU: the n x n column-major tile A := L\\U (L unit lower); info (device int, optional) receives the 1-based index of the "
      "first zero pivot; invL / invU (optional, ceil(n/64) x 4096 doubles) the inverses of the 64 x 64 diagonal blocks of L and U");
+  m.def("kernel_dtrtri", [](uintptr_t A, int n, int lda, uintptr_t info, int info_base, uintptr_t W, int ldw, uintptr_t stream) {
+    return parsec_amd_dtrtri_tile((double*)A, n, lda, (int*)info, info_base, (double*)W, ldw, (void*)stream);
+  }, py::arg("A"), py::arg("n"), py::arg("lda"), py::arg("info") = 0, py::arg("info_base") = 0, py::arg("W") = 0, py::arg("ldw") = 0, py::arg("stream") = 0,
+     "tile TRTRI on the GPU (lower, non-unit): the lower triangle of the n x n column-major tile A := L^-1 in place, or that of W (ld ldw) with A left intact; "
+     "the strict upper triangle is neither read nor written. info (device int, optional) receives info_base + the 1-based index of the first zero diagonal entry");
+  m.def("kernel_dtrmm_lt", [](uintptr_t L, uintptr_t B, int n, int nrhs, int ldl, int ldb, double alpha, uintptr_t stream) {
+    TrmmDesc t{(const double*)L, (double*)B, n, nrhs, ldl, ldb, alpha, 0};
+    return parsec_amd_dtrmm_lt_batch(&t, 1, (void*)stream);
+  }, py::arg("L"), py::arg("B"), py::arg("n"), py::arg("nrhs"), py::arg("ldl"), py::arg("ldb"), py::arg("alpha") = 1.0, py::arg("stream") = 0,
+     "B := alpha L^T B in place on the GPU: L n x n lower (column-major, its strict upper triangle is never read), B n x nrhs");
+  // grouped launch: tuples (L, B, n, nrhs, ldl, ldb, alpha)
+  m.def("kernel_dtrmm_lt_batch", [](const std::vector<py::tuple>& ds, uintptr_t stream) {
+    std::vector<TrmmDesc> v;
+    for (const auto& d : ds) {
+      if (d.size() != 7) throw std::invalid_argument("kernel_dtrmm_lt_batch: tuples of (L, B, n, nrhs, ldl, ldb, alpha)");
+      v.push_back(TrmmDesc{(const double*)d[0].cast<uintptr_t>(), (double*)d[1].cast<uintptr_t>(), d[2].cast<int>(), d[3].cast<int>(), d[4].cast<int>(),
+                           d[5].cast<int>(), d[6].cast<double>(), 0});
+    }
+    return parsec_amd_dtrmm_lt_batch(v.data(), (int)v.size(), (void*)stream);
+  }, py::arg("descs"), py::arg("stream") = 0, "B := alpha L^T B for every descriptor in one grouped launch");
+  m.def("kernel_dlauum", [](uintptr_t A, int n, int lda, uintptr_t stream) { return parsec_amd_dlauum_tile((double*)A, n, lda, (void*)stream); },
+        py::arg("A"), py::arg("n"), py::arg("lda"), py::arg("stream") = 0,
+        "tile LAUUM on the GPU: the lower triangle of the n x n column-major tile A := lower(L^T L) in place; the strict upper triangle is neither read nor written");
   // grouped launch: tuples (L, B, n, nrhs, ldl, ldb, alpha, trans[, upper[, unit[, right]]])
   m.def("kernel_dtrsm_left_batch", [](const std::vector<py::tuple>& ds, uintptr_t stream) {
     std::vector<TrsmLeftDesc> v;

@@ -708,6 +708,24 @@ parsec_taskpool_t* parsec_dgels_New(parsec_tiled_matrix_t* A, parsec_tiled_matri
 parsec_taskpool_t* parsec_dgetrf_nopiv_New(parsec_tiled_matrix_t* A, int* info);
 parsec_taskpool_t* parsec_dgetrs_nopiv_New(parsec_matrix_trans_t trans, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B);
 parsec_taskpool_t* parsec_dgesv_nopiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info);
+/* The inverse with the Cholesky factor (DPLASMA's dplasma_dtrtri_New /
+ * dlauum / dpotri / dpoinv roles; the ptgpp-compiled dtrtri_L.jdf and
+ * dlauum_L.jdf) of a square double matrix with square tiles (a ragged last tile
+ * is allowed), PARSEC_MATRIX_LOWER only. Only A's lower tiles and the lower
+ * triangles of its diagonal tiles are read and written: symmetrise the result
+ * if the full inverse is needed. parsec_dtrtri_New (PARSEC_MATRIX_NONUNIT): A :=
+ * L^-1; *info (optional) holds the 1-based global index of the first diagonal
+ * entry that is exactly zero once the taskpool completed (0: none).
+ * parsec_dlauum_New: A := lower(L^T L). parsec_dpotri_New: the two composed, the
+ * inverse from the factor parsec_dpotrf_New left in A. parsec_dpoinv_New:
+ * factor, then invert, in one taskpool; with *info != 0 the inverse does not
+ * run and A holds what the factorization left; info is required; one rank only.
+ * All return NULL (after a warning) for any other request or shape; release the
+ * two composed ones with parsec_taskpool_free. */
+parsec_taskpool_t* parsec_dtrtri_New(parsec_matrix_uplo_t uplo, parsec_matrix_diag_t diag, parsec_tiled_matrix_t* A, int* info);
+parsec_taskpool_t* parsec_dlauum_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A);
+parsec_taskpool_t* parsec_dpotri_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A);
+parsec_taskpool_t* parsec_dpoinv_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, int* info);
 int parsec_apply(parsec_context_t* parsec, parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_unary_op_t operation, void* op_args);
 /* op(es, src_tile, dest_tile, op_data, m, n) for every tile of dest */
 parsec_taskpool_t* parsec_map_operator_New(const parsec_tiled_matrix_t* src, parsec_tiled_matrix_t* dest, parsec_operator_t op, void* op_data);

@@ -57,6 +57,7 @@ CORE_SOURCES = [
     "csrc/algos/dtrsm_jdf.cpp",
     "csrc/algos/dgels_jdf.cpp",
     "csrc/algos/dgetrf_jdf.cpp",
+    "csrc/algos/dpotri_jdf.cpp",
     "csrc/algos/redistribute_ptg.cpp",
 ]
 HIP_SOURCES = [
@@ -74,6 +75,8 @@ JDF_SOURCES = [
     "csrc/algos/jdf/dtrsm_LL.jdf",
     "csrc/algos/jdf/dtrsm_LU.jdf",
     "csrc/algos/jdf/dgetrf_nopiv.jdf",
+    "csrc/algos/jdf/dtrtri_L.jdf",
+    "csrc/algos/jdf/dlauum_L.jdf",
     "csrc/algos/jdf/dormqr.jdf",
     "csrc/algos/jdf/redistribute.jdf",
     "csrc/algos/jdf/redistribute_reshuffle.jdf",
@@ -81,7 +84,7 @@ JDF_SOURCES = [
 ]
 # runtime sources that include generated JDF headers
 JDF_USERS = ["csrc/algos/dpotrf_jdf.cpp", "csrc/algos/dgeqrf_jdf.cpp", "csrc/algos/dtrsm_jdf.cpp", "csrc/algos/dgels_jdf.cpp",
-             "csrc/algos/dgetrf_jdf.cpp", "csrc/algos/redistribute_ptg.cpp"]
+             "csrc/algos/dgetrf_jdf.cpp", "csrc/algos/dpotri_jdf.cpp", "csrc/algos/redistribute_ptg.cpp"]
 FORTRAN_SOURCES = ["csrc/fortran/parsecf.F90", "csrc/fortran/parsec_profilef.F90"]
 FLANG = os.path.join(ROCM, "lib", "llvm", "bin", "flang")
 TEST_SOURCES = ["tests/native/test_containers.cpp", "tests/native/test_futures.cpp", "tests/native/test_fetch_queue.cpp"]
@@ -278,7 +281,7 @@ def generate_sanitized(kind):
     # Cholesky (ptgpp-compiled dpotrf_L.jdf, CPU bodies on 1..4 ranks); the
     # factor-and-solve program (dtrsm_LL.jdf) is built beside them
     for capi in ("tests/capi/dtd_capi.c", "tests/capi/dpotrf_capi.c", "tests/capi/dpotrs_capi.c", "tests/capi/dgels_capi.c",
-                 "tests/capi/dgetrf_capi.c"):
+                 "tests/capi/dgetrf_capi.c", "tests/capi/dpotri_capi.c"):
         if not os.path.exists(os.path.join(ROOT, capi)):
             continue
         name = os.path.splitext(os.path.basename(capi))[0]
