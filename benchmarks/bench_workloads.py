@@ -7,12 +7,12 @@
            GPU bodies, Gpoint-updates/s and GFLOP/s at 8 flop/point (config 5)
   dtd_gemm DTD tiled DGEMM C += A B on 4 x 4 tiles, CPU bodies in one process
            (config 1, the plumbing check), GFLOP/s
-  potrs    solve with the Cholesky factor (DPOTRS = the two dtrsm_LL.jdf sweeps):
+  potrs    solve with the Cholesky factor (DPOTRS = the two lower dtrsm_left.jdf sweeps):
            A factored once outside the timed region, every timed step restores B
            and solves, GFLOP/s with 2 N^2 NRHS; the same process then times
            torch.cholesky_solve on the dense factor (what a user does without it)
   gels     least squares with the tile QR factor, M >= N: DGEQRS (dormqr.jdf then
-           dtrsm_LU.jdf on a factor computed once outside the timed region) and
+           dtrsm_left.jdf on a factor computed once outside the timed region) and
            DGELS (DGEQRF + DGEQRS in one taskpool), B (and for DGELS A, T)
            restored every timed step, GFLOP/s with 4 M N NRHS - N^2 NRHS (plus
            2 M N^2 - 2/3 N^3 for DGELS); the same process then times a torch
@@ -354,7 +354,7 @@ def bench_potrs(args):
     dty = (time.perf_counter() - t0) / args.steps
     diff = float(torch.linalg.norm(X - Y) / torch.linalg.norm(Y))
     ctx.fini()
-    out = {"metric": "GFLOP/s DPOTRS (dtrsm_LL.jdf, HBM-resident tiles, B restored every step)", "value": round(flops / dt / 1e9, 1), "unit": "GFLOP/s",
+    out = {"metric": "GFLOP/s DPOTRS (dtrsm_left.jdf, HBM-resident tiles, B restored every step)", "value": round(flops / dt / 1e9, 1), "unit": "GFLOP/s",
            "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "dtype": "fp64",
            "backward_error": resid, "yardstick": "torch.cholesky_solve on the dense factor, same process",
            "yardstick_gflops": round(flops / dty / 1e9, 1), "yardstick_ms": round(dty * 1e3, 3), "ratio_to_yardstick": round(dty / dt, 3),
@@ -479,7 +479,7 @@ def bench_gels(args):
     dty = (time.perf_counter() - t0) / args.steps
     diff = float(torch.linalg.norm(X - Y) / torch.linalg.norm(Y))
     ctx.fini()
-    out = {"metric": "GFLOP/s DGEQRS (dormqr.jdf + dtrsm_LU.jdf, HBM-resident tiles, B restored every step)", "value": round(flops_solve / dt_geqrs / 1e9, 1),
+    out = {"metric": "GFLOP/s DGEQRS (dormqr.jdf + dtrsm_left.jdf, HBM-resident tiles, B restored every step)", "value": round(flops_solve / dt_geqrs / 1e9, 1),
            "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(dt_geqrs * 1e3, 3), "higher_is_better": True,
            "dtype": "fp64", "normal_equations_residual": resid,
            "dgels_gflops": round((flops_qr + flops_solve) / dt_gels / 1e9, 1), "dgels_ms": round(dt_gels * 1e3, 3), "dgels_normal_equations_residual": resid_gels,

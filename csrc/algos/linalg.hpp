@@ -18,7 +18,7 @@ ptg::PtgTaskpool* dpotrf_new(TiledMatrix* A, int uplo, int* info_host);
 ptg::PtgTaskpool* dpotrf_jdf_new(TiledMatrix* A, int* info_host);
 int dpotrf_fuse_syrk(int set);  // SYRK(k-1,k) fused into POTRF(k) in new dpotrf_L.jdf taskpools; set < 0 queries
 // Tiled triangular solve B := alpha op(A)^-1 B from the JDF source
-// algos/jdf/dtrsm_LL.jdf: side Left, uplo Lower, trans NoTrans or Trans, diag
+// algos/jdf/dtrsm_left.jdf: side Left, uplo Lower, trans NoTrans or Trans, diag
 // NonUnit (MatrixSide / MatrixUplo / MatrixTrans / MatrixDiag). A is N x N with
 // square tiles, B is N x NRHS with B->mb == A->nb; A and B may be distributed
 // differently. Any other request returns nullptr after a warning.
@@ -62,7 +62,7 @@ Taskpool* dpoinv_new(int uplo, TiledMatrix* A, int* info);
 // Anything else returns nullptr after a warning.
 ptg::PtgTaskpool* dgetrf_nopiv_new(TiledMatrix* A, int* info_host);
 // Solve op(A) X = B with the factor dgetrf_nopiv_new left in A: trans NoTrans
-// (the unit L sweep of dtrsm_LL.jdf, then the U sweep of dtrsm_LU.jdf) or Trans
+// (the unit L sweep of dtrsm_left.jdf, then its U sweep) or Trans
 // (U^T, then L^T). B is N x NRHS with B->mb == A->nb, any tile width, any
 // distribution, and is overwritten with X. Freeing the returned taskpool
 // (taskpool_free) frees the two sweeps.
@@ -88,7 +88,7 @@ ptg::PtgTaskpool* dgeqrf_jdf_new(TiledMatrix* A, TiledMatrix* T);
 // after a warning.
 ptg::PtgTaskpool* dormqr_new(int side, int trans, TiledMatrix* A, TiledMatrix* T, TiledMatrix* B);
 // The minimiser of ||A X - B||_F (M >= N) from that factor: Q^T B composed with
-// the solve with R (algos/jdf/dtrsm_LU.jdf). On return rows 0..N-1 of B hold X
+// the solve with R (algos/jdf/dtrsm_left.jdf). On return rows 0..N-1 of B hold X
 // and rows N..M-1 the residual components, whose column norms are the residual
 // norms (LAPACK DGELS convention). A singular R yields inf / nan as in LAPACK.
 // Freeing the returned taskpool (taskpool_free) frees its parts.

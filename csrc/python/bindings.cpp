@@ -112,6 +112,22 @@ static py::object dtd_arg(Task* t, int i) {
 template <class M>
 static void bind_tiled_common(py::class_<M, TiledMatrix>& c) { (void)c; }
 
+// (taskpool, info address) for a taskpool that reports through an info word:
+// make(int*) creates the taskpool, which then owns the word; None when make
+// refuses the request
+template <class Make>
+static py::object with_info_word(Make make, py::return_value_policy policy) {
+  auto* info = new int(0);
+  auto* tp = make(info);
+  if (!tp) {
+    delete info;
+    return py::none();
+  }
+  auto prev = tp->destructor_hook;
+  tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
+  return py::make_tuple(py::cast(tp, policy), (uintptr_t)info);
+}
+
 // every GemmDesc field but the gate protocol (that runs through kernel_trsm_w_batch); missing keys are 0
 static std::vector<GemmDesc> gemm_descs_from_dicts(const std::vector<py::dict>& ds, const std::string& who) {
   static const char* const known[] = {"A", "B", "C", "m", "n", "k", "lda", "ldb", "ldc", "alpha", "beta", "transA", "transB", "lower_only", "a_lower",
@@ -546,65 +562,28 @@ PYBIND11_MODULE(_C, m) {
       .def("set_entry", [](HashCollection& h, uint64_t key, uint32_t rank, int32_t vp, uintptr_t ptr, size_t size) { h.set_entry(key, rank, vp, (void*)ptr, size); });
 
   // ---------------------------------------------------------------- algos
-  m.def("dpotrf_new", [](TiledMatrix* A, int uplo) {
-        auto* info = new int(0);
-        auto* tp = algos::dpotrf_new(A, uplo, info);
-        tp->destructor_hook = [info]() { delete info; };
-        return py::make_tuple(py::cast(tp, py::return_value_policy::take_ownership), (uintptr_t)info);
-      });
+  constexpr auto owned = py::return_value_policy::take_ownership, composed = py::return_value_policy::reference;
+  m.def("dpotrf_new", [](TiledMatrix* A, int uplo) { return with_info_word([&](int* info) { return algos::dpotrf_new(A, uplo, info); }, owned); });
   m.def("dpotrf_fuse_syrk", [](int set) { return algos::dpotrf_fuse_syrk(set); }, py::arg("set") = -1,
         "SYRK(k-1,k) fused into POTRF(k) for new dpotrf_L.jdf taskpools (PARSEC_DPOTRF_FUSE_SYRK); returns the previous value");
-  m.def("dpotrf_jdf_new", [](TiledMatrix* A) {
-        auto* info = new int(0);
-        auto* tp = algos::dpotrf_jdf_new(A, info);
-        auto prev = tp->destructor_hook;
-        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
-        return py::make_tuple(py::cast(tp, py::return_value_policy::take_ownership), (uintptr_t)info);
-      }, "tiled Cholesky (lower) from the ptgpp-compiled algos/jdf/dpotrf_L.jdf; returns (taskpool, info address)");
+  m.def("dpotrf_jdf_new", [](TiledMatrix* A) { return with_info_word([&](int* info) { return algos::dpotrf_jdf_new(A, info); }, owned); },
+        "tiled Cholesky (lower) from the ptgpp-compiled algos/jdf/dpotrf_L.jdf; returns (taskpool, info address)");
   m.def("dtrsm_new", [](int side, int uplo, int trans, int diag, double alpha, TiledMatrix* A, TiledMatrix* B) {
         return algos::dtrsm_new(side, uplo, trans, diag, alpha, A, B);
       }, py::arg("side"), py::arg("uplo"), py::arg("trans"), py::arg("diag"), py::arg("alpha"), py::arg("A"), py::arg("B"), py::return_value_policy::take_ownership,
       "tiled triangular solve B := alpha op(A)^-1 B (MATRIX_LEFT, MATRIX_LOWER, MATRIX_NOTRANS / MATRIX_TRANS, MATRIX_NONUNIT) from the ptgpp-compiled "
-      "dtrsm_LL.jdf; B.mb must equal A.nb; None for anything else");
+      "dtrsm_left.jdf; B.mb must equal A.nb; None for anything else");
   // composed taskpools: release with taskpool_free (it frees the parts too)
   m.def("dpotrs_new", [](int uplo, TiledMatrix* A, TiledMatrix* B) { return algos::dpotrs_new(uplo, A, B); }, py::arg("uplo"), py::arg("A"), py::arg("B"),
         py::return_value_policy::reference, "solve A X = B with the Cholesky factor in A (lower): B := L^-T L^-1 B; None on invalid arguments");
-  m.def("dposv_new", [](int uplo, TiledMatrix* A, TiledMatrix* B) -> py::object {
-        auto* info = new int(0);
-        Taskpool* tp = algos::dposv_new(uplo, A, B, info);
-        if (!tp) {
-          delete info;
-          return py::none();
-        }
-        auto prev = tp->destructor_hook;
-        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
-        return py::make_tuple(py::cast(tp, py::return_value_policy::reference), (uintptr_t)info);
-      }, py::arg("uplo"), py::arg("A"), py::arg("B"),
+  m.def("dposv_new", [](int uplo, TiledMatrix* A, TiledMatrix* B) { return with_info_word([&](int* info) { return algos::dposv_new(uplo, A, B, info); }, composed); },
+      py::arg("uplo"), py::arg("A"), py::arg("B"),
       "Cholesky factorization then solve (lower, one rank); returns (taskpool, info address) or None. When info != 0 the solve does not run and B is untouched");
-  m.def("dgetrf_nopiv_new", [](TiledMatrix* A) -> py::object {
-        auto* info = new int(0);
-        auto* tp = algos::dgetrf_nopiv_new(A, info);
-        if (!tp) {
-          delete info;
-          return py::none();
-        }
-        auto prev = tp->destructor_hook;
-        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
-        return py::make_tuple(py::cast(tp, py::return_value_policy::take_ownership), (uintptr_t)info);
-      }, py::arg("A"),
+  m.def("dgetrf_nopiv_new", [](TiledMatrix* A) { return with_info_word([&](int* info) { return algos::dgetrf_nopiv_new(A, info); }, owned); }, py::arg("A"),
       "tiled LU WITHOUT pivoting (square A, square tiles) from the ptgpp-compiled dgetrf_nopiv.jdf: A := L\\U, L unit lower; returns (taskpool, info address) or "
       "None. info is the 1-based index of the first pivot that is exactly zero; the matrix must not need pivoting");
-  m.def("dtrtri_new", [](int uplo, int diag, TiledMatrix* A) -> py::object {
-        auto* info = new int(0);
-        auto* tp = algos::dtrtri_new(uplo, diag, A, info);
-        if (!tp) {
-          delete info;
-          return py::none();
-        }
-        auto prev = tp->destructor_hook;
-        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
-        return py::make_tuple(py::cast(tp, py::return_value_policy::take_ownership), (uintptr_t)info);
-      }, py::arg("uplo"), py::arg("diag"), py::arg("A"),
+  m.def("dtrtri_new", [](int uplo, int diag, TiledMatrix* A) { return with_info_word([&](int* info) { return algos::dtrtri_new(uplo, diag, A, info); }, owned); },
+      py::arg("uplo"), py::arg("diag"), py::arg("A"),
       "tiled inverse of a lower triangular matrix in place (MATRIX_LOWER, MATRIX_NONUNIT; square A, square tiles) from the ptgpp-compiled dtrtri_L.jdf; returns "
       "(taskpool, info address) or None. info is the 1-based index of the first diagonal entry that is exactly zero. Only the lower tiles / triangles are touched");
   m.def("dlauum_new", [](int uplo, TiledMatrix* A) { return algos::dlauum_new(uplo, A); }, py::arg("uplo"), py::arg("A"),
@@ -612,34 +591,16 @@ PYBIND11_MODULE(_C, m) {
   m.def("dpotri_new", [](int uplo, TiledMatrix* A) { return algos::dpotri_new(uplo, A); }, py::arg("uplo"), py::arg("A"),
         py::return_value_policy::reference,
         "the inverse from the Cholesky factor in A (lower): dtrtri then dlauum, the lower triangle of A := A^-1; None on invalid arguments. Release with taskpool_free");
-  m.def("dpoinv_new", [](int uplo, TiledMatrix* A) -> py::object {
-        auto* info = new int(0);
-        Taskpool* tp = algos::dpoinv_new(uplo, A, info);
-        if (!tp) {
-          delete info;
-          return py::none();
-        }
-        auto prev = tp->destructor_hook;
-        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
-        return py::make_tuple(py::cast(tp, py::return_value_policy::reference), (uintptr_t)info);
-      }, py::arg("uplo"), py::arg("A"),
+  m.def("dpoinv_new", [](int uplo, TiledMatrix* A) { return with_info_word([&](int* info) { return algos::dpoinv_new(uplo, A, info); }, composed); },
+      py::arg("uplo"), py::arg("A"),
       "Cholesky factorization then inverse (lower, one rank); returns (taskpool, info address) or None. When info != 0 the inverse does not run and A holds what "
       "the factorization left");
   m.def("dgetrs_nopiv_new", [](int trans, TiledMatrix* A, TiledMatrix* B) { return algos::dgetrs_nopiv_new(trans, A, B); }, py::arg("trans"), py::arg("A"),
         py::arg("B"), py::return_value_policy::reference,
         "solve op(A) X = B with the factor of dgetrf_nopiv_new in A (MATRIX_NOTRANS or MATRIX_TRANS); B.mb must equal A.nb; None on invalid arguments. Release "
         "with taskpool_free");
-  m.def("dgesv_nopiv_new", [](TiledMatrix* A, TiledMatrix* B) -> py::object {
-        auto* info = new int(0);
-        Taskpool* tp = algos::dgesv_nopiv_new(A, B, info);
-        if (!tp) {
-          delete info;
-          return py::none();
-        }
-        auto prev = tp->destructor_hook;
-        tp->destructor_hook = [info, prev]() { if (prev) prev(); delete info; };
-        return py::make_tuple(py::cast(tp, py::return_value_policy::reference), (uintptr_t)info);
-      }, py::arg("A"), py::arg("B"),
+  m.def("dgesv_nopiv_new", [](TiledMatrix* A, TiledMatrix* B) { return with_info_word([&](int* info) { return algos::dgesv_nopiv_new(A, B, info); }, composed); },
+      py::arg("A"), py::arg("B"),
       "LU without pivoting then solve (one rank); returns (taskpool, info address) or None. When info != 0 the solve does not run and B is untouched");
   m.def("dormqr_new", [](int side, int trans, TiledMatrix* A, TiledMatrix* T, TiledMatrix* B) { return (Taskpool*)algos::dormqr_new(side, trans, A, T, B); },
         py::arg("side"), py::arg("trans"), py::arg("A"), py::arg("T"), py::arg("B"), py::return_value_policy::reference,

@@ -662,7 +662,7 @@ parsec_taskpool_t* parsec_apply_New(parsec_matrix_uplo_t uplo, parsec_tiled_matr
  * holds the LAPACK info once the taskpool completed (0: success). */
 parsec_taskpool_t* parsec_dpotrf_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, int* info);
 /* Tiled triangular solve B := alpha op(A)^-1 B of double matrices (DPLASMA's
- * dplasma_dtrsm_New role, the ptgpp-compiled dtrsm_LL.jdf): PARSEC_MATRIX_LEFT,
+ * dplasma_dtrsm_New role, the ptgpp-compiled dtrsm_left.jdf): PARSEC_MATRIX_LEFT,
  * PARSEC_MATRIX_LOWER, PARSEC_MATRIX_NOTRANS or PARSEC_MATRIX_TRANS,
  * PARSEC_MATRIX_NONUNIT. A is N x N with square tiles, B is N x NRHS with
  * B->mb == A->nb; the two may be distributed on different process grids. NULL
@@ -677,7 +677,7 @@ parsec_taskpool_t* parsec_dpotrs_New(parsec_matrix_uplo_t uplo, parsec_tiled_mat
  * One rank only: NULL on more (factor, check info, then parsec_dpotrs_New). */
 parsec_taskpool_t* parsec_dposv_New(parsec_matrix_uplo_t uplo, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info);
 /* Least squares with the tile QR factor (DPLASMA's dplasma_dormqr_New /
- * dgeqrs / dgels roles; the ptgpp-compiled dormqr.jdf and dtrsm_LU.jdf). A is
+ * dgeqrs / dgels roles; the ptgpp-compiled dormqr.jdf and dtrsm_left.jdf). A is
  * M x N with square tiles, T (tiled like A) holds the block reflectors, B is
  * M x NRHS with B->mb == A->mb; A / T and B may be distributed on different
  * process grids. The factor must come from the flat-tree QR (parsec_dgels_New

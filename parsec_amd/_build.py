@@ -54,9 +54,8 @@ CORE_SOURCES = [
     "csrc/capi/hash_table.cpp", "csrc/capi/object.cpp", "csrc/capi/future_c.cpp", "csrc/capi/mpi_shim.cpp", "csrc/capi/redistribute_core.cpp",
     "csrc/algos/dpotrf_jdf.cpp",
     "csrc/algos/dgeqrf_jdf.cpp",
-    "csrc/algos/dtrsm_jdf.cpp",
-    "csrc/algos/dgels_jdf.cpp",
-    "csrc/algos/dgetrf_jdf.cpp",
+    "csrc/algos/jdf_glue.cpp",
+    "csrc/algos/solvers_jdf.cpp",
     "csrc/algos/dpotri_jdf.cpp",
     "csrc/algos/redistribute_ptg.cpp",
 ]
@@ -72,8 +71,7 @@ PTGPP_SOURCES = ["tools/ptgpp/ptgpp.cpp"]
 JDF_SOURCES = [
     "csrc/algos/jdf/dpotrf_L.jdf",
     "csrc/algos/jdf/dgeqrf.jdf",
-    "csrc/algos/jdf/dtrsm_LL.jdf",
-    "csrc/algos/jdf/dtrsm_LU.jdf",
+    "csrc/algos/jdf/dtrsm_left.jdf",
     "csrc/algos/jdf/dgetrf_nopiv.jdf",
     "csrc/algos/jdf/dtrtri_L.jdf",
     "csrc/algos/jdf/dlauum_L.jdf",
@@ -83,8 +81,8 @@ JDF_SOURCES = [
     "csrc/algos/jdf/diag_band_to_rect.jdf",
 ]
 # runtime sources that include generated JDF headers
-JDF_USERS = ["csrc/algos/dpotrf_jdf.cpp", "csrc/algos/dgeqrf_jdf.cpp", "csrc/algos/dtrsm_jdf.cpp", "csrc/algos/dgels_jdf.cpp",
-             "csrc/algos/dgetrf_jdf.cpp", "csrc/algos/dpotri_jdf.cpp", "csrc/algos/redistribute_ptg.cpp"]
+JDF_USERS = ["csrc/algos/dpotrf_jdf.cpp", "csrc/algos/dgeqrf_jdf.cpp", "csrc/algos/solvers_jdf.cpp", "csrc/algos/dpotri_jdf.cpp",
+             "csrc/algos/redistribute_ptg.cpp"]
 FORTRAN_SOURCES = ["csrc/fortran/parsecf.F90", "csrc/fortran/parsec_profilef.F90"]
 FLANG = os.path.join(ROCM, "lib", "llvm", "bin", "flang")
 TEST_SOURCES = ["tests/native/test_containers.cpp", "tests/native/test_futures.cpp", "tests/native/test_fetch_queue.cpp"]
@@ -279,7 +277,7 @@ def generate_sanitized(kind):
         lines.append(f"  libs = -L{out} -lparsec_amd -Wl,-rpath,{out} {libs}")
     # C API programs run instrumented: the DTD program and the distributed PTG
     # Cholesky (ptgpp-compiled dpotrf_L.jdf, CPU bodies on 1..4 ranks); the
-    # factor-and-solve program (dtrsm_LL.jdf) is built beside them
+    # factor-and-solve program (dtrsm_left.jdf) is built beside them
     for capi in ("tests/capi/dtd_capi.c", "tests/capi/dpotrf_capi.c", "tests/capi/dpotrs_capi.c", "tests/capi/dgels_capi.c",
                  "tests/capi/dgetrf_capi.c", "tests/capi/dpotri_capi.c"):
         if not os.path.exists(os.path.join(ROOT, capi)):

@@ -4,7 +4,7 @@ bodies), dgeqrf then dgeqrs, and dgels in one taskpool.
 A and T (M x N, nb x nb tiles) live on a PA x QA grid and B (M x NRHS, nb x nbr
 tiles) on a PB x QB grid of the same ranks: V and T reach the tasks, which run
 where their B tile lives, through the reader tasks of dormqr.jdf, the tiles of R
-through those of dtrsm_LU.jdf. Every rank writes its tiles of the two results
+through those of dtrsm_left.jdf. Every rank writes its tiles of the two results
 (dgeqrs<rank>.npy, dgels<rank>.npy, zeros elsewhere) into outdir; the test adds
 them up and checks the residuals. The same matrices as the test: seed 13.
 argv: rank size job M N nb NRHS nbr PA QA PB QB outdir"""

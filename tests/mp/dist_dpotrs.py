@@ -3,7 +3,7 @@
 A (the Cholesky factor, N x N, nb x nb tiles) lives on a PA x QA grid and B
 (N x NRHS, nb x nbr tiles) on a PB x QB grid of the same ranks: the tiles of L
 reach the tasks, which run where their B tile lives, through the reader tasks
-of dtrsm_LL.jdf."""
+of dtrsm_left.jdf."""
 import os
 import sys
 
