@@ -24,6 +24,14 @@
            ||L U - A||_F / ||A||_F; the same process then times
            torch.linalg.lu_factor / lu_solve on the dense data -- torch PIVOTS
            (partial pivoting), so the yardstick does more work than we do
+  getrf_incpiv  tile LU with incremental (pairwise) pivoting on a seeded standard
+           normal matrix (it needs pivoting): DGETRF_INCPIV and DGESV_INCPIV
+           with A, L and B restored every timed step; GFLOP/s credited with
+           2/3 N^3 (+ 2 N^2 NRHS), the flops executed (GETRF 2/3, GESSM 1,
+           TSTRF 1, SSSSM 3 nb^3 each: about N^3) printed beside it; the same
+           process then times torch.linalg.lu_factor / lu_solve, and the solve
+           residual ||A X - B||_F / (||A||_F ||X||_F + ||B||_F) is printed for
+           ours and torch's
   potri    the inverse with the Cholesky factor of a seeded SPD matrix: DTRTRI
            (N^3 / 3) and DPOTRI (2/3 N^3) on the dense factor torch computed,
            DPOINV (N^3) on the matrix, A restored every timed step; the same
@@ -39,6 +47,7 @@ Multi-GPU: launch like bench.py (torch.distributed.run, one rank per GPU).
     python benchmarks/bench_workloads.py potrs --n 16384 --nb 512 --nrhs 16384
     python benchmarks/bench_workloads.py gels --m 32768 --n 8192 --nb 512 --nrhs 512
     python benchmarks/bench_workloads.py getrf --n 16384 --nb 512 --nrhs 512
+    python benchmarks/bench_workloads.py getrf_incpiv --n 16384 --nb 512 --nrhs 512
     python benchmarks/bench_workloads.py potri --n 16384 --nb 512
 """
 import argparse
@@ -616,6 +625,139 @@ def bench_getrf(args):
     return out, 0
 
 
+def bench_getrf_incpiv(args):
+    import torch
+
+    import parsec_amd as pa
+
+    world, rank, local = _dist()
+    if world > 1:
+        raise RuntimeError("getrf_incpiv: one GPU (the yardstick is a single-device torch.linalg.lu_factor)")
+    if not torch.cuda.is_available():
+        raise RuntimeError("getrf_incpiv: no GPU")
+    N, nb, NRHS = args.n, args.nb, args.nrhs
+    nbr = args.nbr or min(nb, NRHS)
+    dev = torch.device("cuda", 0)
+    ctx = pa.init(args.cores)
+    gpu = pa.first_gpu_device_index()
+    if gpu < 0:
+        raise RuntimeError("no GPU device registered in the runtime")
+    NT, NTB = -(-N // nb), -(-NRHS // nbr)
+
+    def run(tp):
+        ctx.add_taskpool(tp)
+        ctx.start()
+        ctx.wait()
+
+    def tiled(dense, rows, cols, mt, nt, mb, cb):  # the store image [n][m][col][row] of a dense matrix
+        pad = torch.zeros((mt * mb, nt * cb), dtype=torch.float64, device=dev)
+        pad[:rows, :cols] = dense
+        return pad.reshape(mt, mb, nt, cb).permute(2, 0, 3, 1).contiguous()
+
+    def dense_of(store, rows, cols, mb, cb):  # a dense COPY of a tiled store
+        return store.permute(1, 3, 0, 2).reshape(store.shape[1] * mb, store.shape[0] * cb)[:rows, :cols].contiguous()
+
+    # standard normal: partial pivoting swaps almost every row, an unpivoted LU is unusable
+    gen = torch.Generator(device=dev).manual_seed(12345)
+    S = torch.randn((N, N), dtype=torch.float64, device=dev, generator=gen)
+    B0 = torch.randn((N, NRHS), dtype=torch.float64, device=dev, generator=gen)
+    backupA = tiled(S, N, N, NT, NT, nb, nb)
+    backupB = tiled(B0, N, NRHS, NT, NTB, nb, nbr)
+    sa = backupA.clone()
+    sl = torch.zeros_like(sa)
+    sb = backupB.clone()
+    A = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nb, N, N, device=gpu, ptr=sa.data_ptr())
+    L = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nb, N, N, device=gpu, ptr=sl.data_ptr())
+    B = pa.BlockCyclic(pa.MATRIX_DOUBLE, 0, nb, nbr, N, NRHS, device=gpu, ptr=sb.data_ptr())
+    torch.cuda.synchronize()
+    infos = []
+
+    def step_getrf():
+        sa.copy_(backupA)
+        sl.zero_()
+        torch.cuda.synchronize()
+        r = pa.dgetrf_incpiv_new(A, L)
+        if r is None:
+            raise RuntimeError("dgetrf_incpiv_new refused the request")
+        run(r[0])
+        infos.append(pa.read_int(r[1]))
+
+    def step_gesv():
+        sa.copy_(backupA)
+        sl.zero_()
+        sb.copy_(backupB)
+        torch.cuda.synchronize()
+        tp, info = pa.dgesv_incpiv_new(A, L, B)
+        run(tp)
+        infos.append(pa.read_int(info))
+        pa.taskpool_free(tp)
+
+    def timed(step):
+        for _ in range(args.warmup):
+            step()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) / args.steps
+
+    dt_getrf = timed(step_getrf)
+    dt_gesv = timed(step_gesv)
+    if any(infos):
+        raise RuntimeError(f"a zero on U's diagonal was reported: info {infos}")
+    nS = torch.linalg.norm(S)
+
+    def residual(X):
+        return float(torch.linalg.norm(S @ X - B0) / (nS * torch.linalg.norm(X) + torch.linalg.norm(B0)))
+
+    X = dense_of(sb, N, NRHS, nb, nbr)
+    resid = residual(X)
+    max_mult = float(torch.tril(dense_of(sa, N, N, nb, nb), -1).abs().max())
+    flops_lu = 2.0 / 3.0 * N ** 3
+    flops_sv = flops_lu + 2.0 * N * N * NRHS
+    # executed: GETRF 2/3, GESSM 1, TSTRF 1, SSSSM 3 (solve with the full L1 + one K = nb GEMM), in nb^3
+    pairs = NT * (NT - 1) / 2.0
+    exec_lu = (2.0 / 3.0 * NT + 2.0 * pairs + 3.0 * (NT - 1) * NT * (2 * NT - 1) / 6.0) * float(nb) ** 3
+    exec_sv = exec_lu + (NT + 3.0 * pairs) * float(nb) ** 2 * NRHS + float(N) * N * NRHS
+    del sa, sl, backupA
+    # yardstick on the dense data: torch's LU with partial pivoting (out of place, no restore needed)
+    for _ in range(max(1, args.warmup)):
+        LU, piv = torch.linalg.lu_factor(S)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        LU, piv = torch.linalg.lu_factor(S)
+    torch.cuda.synchronize()
+    dty_lu = (time.perf_counter() - t0) / args.steps
+    for _ in range(max(1, args.warmup)):
+        Y = torch.linalg.lu_solve(LU, piv, B0)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        Y = torch.linalg.lu_solve(LU, piv, B0)
+    torch.cuda.synchronize()
+    dty_sv = dty_lu + (time.perf_counter() - t0) / args.steps
+    torch_resid = residual(Y)
+    # pairwise pivoting loses accuracy with the number of tile rows (both figures are
+    # printed); only a result that is no solution at all is an error
+    if not resid < 1e-9:
+        raise RuntimeError(f"solve residual too large: ours {resid:.3e}, torch {torch_resid:.3e}")
+    ctx.fini()
+    out = {"metric": "GFLOP/s DGETRF_INCPIV (dgetrf_incpiv.jdf, pairwise pivoting, credited 2/3 N^3, HBM-resident tiles, A and L restored every step)",
+           "value": round(flops_lu / dt_getrf / 1e9, 1), "unit": "GFLOP/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup,
+           "ms_per_step": round(dt_getrf * 1e3, 3), "higher_is_better": True, "dtype": "fp64", "flops_getrf": flops_lu, "flops_gesv": flops_sv,
+           "executed_flops_getrf": exec_lu, "executed_flops_gesv": exec_sv, "executed_gflops": round(exec_lu / dt_getrf / 1e9, 1),
+           "dgesv_gflops": round(flops_sv / dt_gesv / 1e9, 1), "dgesv_ms": round(dt_gesv * 1e3, 3), "dgesv_residual": resid, "max_multiplier": max_mult,
+           "yardstick": "torch.linalg.lu_factor / lu_solve (partial pivoting) on the dense data, same process",
+           "yardstick_lu_gflops": round(flops_lu / dty_lu / 1e9, 1), "yardstick_lu_ms": round(dty_lu * 1e3, 3),
+           "yardstick_solve_gflops": round(flops_sv / dty_sv / 1e9, 1), "yardstick_solve_ms": round(dty_sv * 1e3, 3), "yardstick_residual": torch_resid,
+           "residual_ratio_to_yardstick": round(resid / torch_resid, 2),
+           "ratio_to_yardstick": round(dty_lu / dt_getrf, 3), "dgesv_ratio_to_yardstick": round(dty_sv / dt_gesv, 3),
+           "config": {"model": "DGETRF_INCPIV", "N": N, "nb": nb, "NRHS": NRHS, "nbr": nbr, "tile_rows": NT, "cores": args.cores}}
+    return out, 0
+
+
 def bench_potri(args):
     import torch
 
@@ -762,7 +904,7 @@ def bench_potri(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm", "potrs", "gels", "getrf", "potri"])
+    ap.add_argument("workload", choices=["qr", "stencil", "dtd_gemm", "potrs", "gels", "getrf", "getrf_incpiv", "potri"])
     ap.add_argument("--n", "--size", dest="n", type=int, default=None, help="matrix order (use --size under torchrun)")
     ap.add_argument("--m", type=int, default=None, help="gels: rows of A (default: n)")
     ap.add_argument("--nb", type=int, default=512)
@@ -784,12 +926,12 @@ def main():
                     help="qr: rows per TS domain of the hierarchical tree (0: one flat TS chain per process row, TT binary tree across process rows; 1 GPU measured fastest flat: profiles/r3_qr_tree_ab.jsonl)")
     args = ap.parse_args()
     if args.n is None:
-        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048, "potrs": 16384, "gels": 16384, "getrf": 16384, "potri": 16384}[args.workload]
+        args.n = {"qr": 16384, "stencil": 512, "dtd_gemm": 2048, "potrs": 16384, "gels": 16384, "getrf": 16384, "getrf_incpiv": 16384, "potri": 16384}[args.workload]
     if args.nrhs is None:
         args.nrhs = args.n
     if args.m is None:
         args.m = args.n
-    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm, "potrs": bench_potrs, "gels": bench_gels, "getrf": bench_getrf, "potri": bench_potri}[args.workload]
+    fn = {"qr": bench_qr, "stencil": bench_stencil, "dtd_gemm": bench_dtd_gemm, "potrs": bench_potrs, "gels": bench_gels, "getrf": bench_getrf, "getrf_incpiv": bench_getrf_incpiv, "potri": bench_potri}[args.workload]
     out, rank = fn(args)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -69,6 +69,21 @@ const char* solve_problem(const TiledMatrix* A, const TiledMatrix* B) {
   return nullptr;
 }
 
+const char* incpiv_problem(const TiledMatrix* A, const TiledMatrix* L) {
+  if (const char* why = factor_problem(A)) return why;
+  if (A->nb > kern::kLuMaxTile) return "the tile size exceeds 1024 (the pivoted tile kernels hold a strip's rows in registers)";
+  if (!L) return "null matrix";
+  if (L->mtype != MATRIX_DOUBLE) return "double precision matrices only";
+  if (L->mb != A->nb || L->nb != A->nb || L->mt != A->mt || L->nt != A->nt) return "L must be tiled like A (nb x nb tiles, one per tile of A)";
+  if (L->nodes != A->nodes) return "L must be distributed like A";
+  for (int64_t m = 0; m < A->mt; ++m)
+    for (int64_t n = 0; n <= m && n < A->nt; ++n) {
+      const int64_t idx[2] = {m, n};
+      if (L->rank_of(idx, 2) != A->rank_of(idx, 2)) return "L must be distributed like A";
+    }
+  return nullptr;
+}
+
 const char* qr_solve_problem(const TiledMatrix* A, const TiledMatrix* T, const TiledMatrix* B) {
   if (!A || !T || !B) return "null matrix";
   if (A->mtype != MATRIX_DOUBLE || T->mtype != MATRIX_DOUBLE || B->mtype != MATRIX_DOUBLE) return "double precision matrices only";

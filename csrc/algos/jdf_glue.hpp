@@ -45,6 +45,10 @@ Taskpool* compose_owned(const char* name, std::initializer_list<Taskpool*> parts
 const char* factor_problem(const TiledMatrix* A);
 // ... and B a right-hand side for it: as many rows as A, B->mb == A->nb
 const char* solve_problem(const TiledMatrix* A, const TiledMatrix* B);
+// A and its companion L for the tile LU with incremental pivoting: A as for
+// factor_problem with a tile of at most 1024, L of the same type, tile size
+// (nb x nb), tile grid and distribution
+const char* incpiv_problem(const TiledMatrix* A, const TiledMatrix* L);
 // A (M x N, square tiles) and T hold a tile QR factor, B has M rows and B->mb == A->mb
 const char* qr_solve_problem(const TiledMatrix* A, const TiledMatrix* T, const TiledMatrix* B);
 

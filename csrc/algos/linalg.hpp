@@ -72,6 +72,29 @@ Taskpool* dgetrs_nopiv_new(int trans, TiledMatrix* A, TiledMatrix* B);
 // taskpools start empty: B is left untouched. `info` is required. One rank only
 // (nullptr otherwise): ranks see only the pivots of their own diagonal tiles.
 Taskpool* dgesv_nopiv_new(TiledMatrix* A, TiledMatrix* B, int* info);
+// Tiled LU factorization with incremental (pairwise) pivoting from the JDF
+// source algos/jdf/dgetrf_incpiv.jdf (PLASMA's / DPLASMA's dgetrf_incpiv): A is
+// square with square tiles of at most 1024, double; a ragged last tile is
+// allowed. L is the companion collection: same type, tile size (nb x nb), tile
+// grid and distribution as A; its tiles (m, k), m >= k, receive a unit lower
+// triangle in their strict lower part and the pivots (LAPACK ipiv values over
+// the stacked rows of a tile pair, stored as doubles) in their last column.
+// `info_host` receives the 1-based global index of the first diagonal entry of
+// the final U that is exactly zero (0 = none); a zero pivot divides nothing, so
+// the factor never holds inf / nan because of one. Anything else returns
+// nullptr after a warning.
+ptg::PtgTaskpool* dgetrf_incpiv_new(TiledMatrix* A, TiledMatrix* L, int* info_host);
+// Solve A X = B with the factor dgetrf_incpiv_new left in A and L (NoTrans only):
+// the recorded interchanges and eliminations applied to B in factorization
+// order (dgetrs_incpiv.jdf), then the U sweep of dtrsm_left.jdf. B is N x NRHS
+// with B->mb == A->nb, any tile width, any distribution, and is overwritten
+// with X. Freeing the returned taskpool (taskpool_free) frees the parts.
+Taskpool* dgetrs_incpiv_new(int trans, TiledMatrix* A, TiledMatrix* L, TiledMatrix* B);
+// dgetrf_incpiv_new composed with dgetrs_incpiv_new. When U has a zero on its
+// diagonal (*info != 0 once the factorization completed) the solve taskpools
+// start empty: B is left untouched. `info` is required. One rank only (nullptr
+// otherwise): ranks see only the zeros of their own tiles.
+Taskpool* dgesv_incpiv_new(TiledMatrix* A, TiledMatrix* L, TiledMatrix* B, int* info);
 // Tiled GEMM C = alpha op(A) op(B) + beta C (PTG; B transposed if transB).
 ptg::PtgTaskpool* dgemm_new(double alpha, TiledMatrix* A, TiledMatrix* B, double beta, TiledMatrix* C, int transB);
 // Tiled QR A = QR (Householder, tile algorithm GEQRT/TSQRT/UNMQR/TSMQR). T holds

@@ -5,7 +5,10 @@
 //   DPOTRS       = solve with L, then with L^T        DPOSV       = DPOTRF, then DPOTRS
 //   DGETRS_NOPIV = unit L, then U (or U^T, then L^T)  DGESV_NOPIV = DGETRF_NOPIV, then DGETRS_NOPIV
 //   DGEQRS       = Q^T B, then solve with R           DGELS       = DGEQRF, then DGEQRS
+//   DGETRS_INCPIV = the recorded L and P, then U      DGESV_INCPIV = DGETRF_INCPIV, then DGETRS_INCPIV
+#include "dgetrf_incpiv.h"
 #include "dgetrf_nopiv.h"
+#include "dgetrs_incpiv.h"
 #include "dormqr.h"
 #include "dtrsm_left.h"
 #include "jdf_glue.hpp"
@@ -126,6 +129,60 @@ Taskpool* dgesv_nopiv_new(TiledMatrix* A, TiledMatrix* B, int* info) {
     return nullptr;
   }
   return compose_owned("dgesv_nopiv", {dgetrf_nopiv_new(A, info), lu_l_sweep(false, A, B, info), lu_u_sweep(false, A, B, info)});
+}
+
+ptg::PtgTaskpool* dgetrf_incpiv_new(TiledMatrix* A, TiledMatrix* L, int* info_host) {
+  if (info_host) *info_host = 0;
+  if (const char* why = incpiv_problem(A, L)) {
+    warning("dgetrf_incpiv_new: %s", why);
+    return nullptr;
+  }
+  const InfoWords w = info_acquire();
+  parsec_dgetrf_incpiv_taskpool_t* tp = parsec_dgetrf_incpiv_new(A, L, w.hip(), w.cpu);
+  tp->taskpool_name = "dgetrf_incpiv.jdf";
+  info_attach(tp, w, info_host);
+  return tp;
+}
+
+// the interchanges and eliminations of the factorization applied to B
+static Taskpool* incpiv_forward(TiledMatrix* A, TiledMatrix* L, TiledMatrix* B, const int* gate) {
+  parsec_dgetrs_incpiv_taskpool_t* tp = parsec_dgetrs_incpiv_new(A, L, B);
+  tp->taskpool_name = "dgetrs_incpiv.jdf";
+  gate_on(tp, gate, &tp->_g_MT);
+  return tp;
+}
+
+// the checks DGETRS_INCPIV and DGESV_INCPIV share
+static bool incpiv_solve_refused(const char* who, const TiledMatrix* A, const TiledMatrix* L, const TiledMatrix* B) {
+  const char* why = incpiv_problem(A, L);
+  if (!why) why = solve_problem(A, B);
+  if (why) warning("%s: %s", who, why);
+  return why != nullptr;
+}
+
+Taskpool* dgetrs_incpiv_new(int trans, TiledMatrix* A, TiledMatrix* L, TiledMatrix* B) {
+  if (trans != MATRIX_NOTRANS) {
+    warning("dgetrs_incpiv_new: trans %d is not implemented (NoTrans only: a transposed solve runs the chain backwards)", trans);
+    return nullptr;
+  }
+  if (incpiv_solve_refused("dgetrs_incpiv_new", A, L, B)) return nullptr;
+  return compose_owned("dgetrs_incpiv", {incpiv_forward(A, L, B, nullptr), lu_u_sweep(false, A, B, nullptr)});
+}
+
+Taskpool* dgesv_incpiv_new(TiledMatrix* A, TiledMatrix* L, TiledMatrix* B, int* info) {
+  if (incpiv_solve_refused("dgesv_incpiv_new", A, L, B)) return nullptr;
+  if (!info) {
+    warning("dgesv_incpiv_new: info is required (the solve is skipped when U has a zero on its diagonal)");
+    return nullptr;
+  }
+  // The solve is gated on this process's info word. Ranks see only the zeros
+  // of their own tiles, so on several ranks they could disagree about running
+  // the solve.
+  if (A->nodes > 1 || B->nodes > 1) {
+    warning("dgesv_incpiv_new: not implemented on more than one rank (compose dgetrf_incpiv and dgetrs_incpiv after checking info)");
+    return nullptr;
+  }
+  return compose_owned("dgesv_incpiv", {dgetrf_incpiv_new(A, L, info), incpiv_forward(A, L, B, info), lu_u_sweep(false, A, B, info)});
 }
 
 static parsec_dormqr_taskpool_t* apply_q_new(bool trans, TiledMatrix* A, TiledMatrix* T, TiledMatrix* B) {

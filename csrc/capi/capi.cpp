@@ -1146,6 +1146,15 @@ parsec_taskpool_t* parsec_dgetrs_nopiv_New(parsec_matrix_trans_t trans, parsec_t
 parsec_taskpool_t* parsec_dgesv_nopiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info) {
   return algos::dgesv_nopiv_new(tm_of(A), tm_of(B), info);
 }
+parsec_taskpool_t* parsec_dgetrf_incpiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* L, int* info) {
+  return algos::dgetrf_incpiv_new(tm_of(A), tm_of(L), info);
+}
+parsec_taskpool_t* parsec_dgetrs_incpiv_New(parsec_matrix_trans_t trans, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* L, parsec_tiled_matrix_t* B) {
+  return algos::dgetrs_incpiv_new((int)trans, tm_of(A), tm_of(L), tm_of(B));
+}
+parsec_taskpool_t* parsec_dgesv_incpiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* L, parsec_tiled_matrix_t* B, int* info) {
+  return algos::dgesv_incpiv_new(tm_of(A), tm_of(L), tm_of(B), info);
+}
 parsec_taskpool_t* parsec_dtrtri_New(parsec_matrix_uplo_t uplo, parsec_matrix_diag_t diag, parsec_tiled_matrix_t* A, int* info) {
   return algos::dtrtri_new((int)uplo, (int)diag, tm_of(A), info);
 }

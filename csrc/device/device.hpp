@@ -175,6 +175,47 @@ struct GetrfDesc {
   int info_base = 0;  // added to the index reported (the tile's first row in the matrix)
 };
 
+// LU with partial pivoting of one tile (GETRF: B == nullptr, T the n x n tile,
+// A := L\U as DGETRF leaves it) or of a stacked pair (TSTRF: S = [T; B] with T
+// n x n upper triangular and B h x n; P S = [L1; L2] U'). 1 <= n, h <= 1024.
+// TSTRF: U' overwrites T's upper triangle (T's strict lower triangle is neither
+// read nor written), L2 overwrites B, the strict lower triangle of L receives
+// L1 (a full unit lower triangle: the interchanges are applied to the computed
+// columns of L too). GETRF: the strict lower triangle of L receives a clean
+// copy of the multipliers. Pivots: LAPACK ipiv values (1-based, sequential)
+// over the stacked rows, 1 .. n a row of T and n+1 .. n+h a row of B, stored as
+// doubles in rows 0 .. n-1 of column `pivcol` of L; nothing else of L is
+// written. A column whose candidates are all exactly zero keeps its row as the
+// pivot and divides nothing; *info (optional) then receives info_base + the
+// 1-based column (the smallest index wins, the word is left alone otherwise).
+struct LuPanelDesc {
+  double* T;
+  int ldt;
+  double* B;
+  int ldb, h;
+  int n;
+  double* L;
+  int ldl, pivcol;
+  int* info = nullptr;  // device pointer (may be null)
+  int info_base = 0;
+};
+
+// Row interchanges of a stacked pair [top (mt rows); bot (h rows, may be null)]
+// over ncols columns: for j = k0 .. k1-1 in sequence, row j of the top tile is
+// exchanged with row piv[j] (1 .. mt a row of the top tile, mt+1 .. mt+h a row
+// of the bottom tile). piv holds doubles (the pivot column of an L tile); an
+// entry outside 1 .. mt+h means "no interchange" and is never used as an address.
+struct LaswpDesc {
+  double* top;
+  double* bot;
+  const double* piv;
+  int ldt, ldb;
+  int mt, h;
+  int ncols;
+  int k0, k1;
+};
+static_assert(sizeof(LaswpDesc) == 56, "LaswpDesc grew: the interchange kernel argument block is sized for 48 of them");
+
 // Inverse of an n x n lower triangular tile, non-unit diagonal (1 <= n <= 1152,
 // lda >= n): A := L^-1 in place, or W_out (ld ldw) := L^-1 with A left intact.
 // Only the lower triangle is read and only the lower triangle of the target is
@@ -246,6 +287,13 @@ void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipS
 void launch_getrf_nopiv(const GetrfDesc& g, hipStream_t stream, double* ws);
 size_t getrf_workspace_bytes(const GetrfDesc& g);
 // tile TRTRI / grouped TRMM (B := alpha L^T B) / tile LAUUM; ws: *_workspace_bytes
+// tile / stacked-pair LU with partial pivoting (lu_kernels.hip); ws:
+// lu_panel_workspace_bytes(). prio: raise the waves' issue priority
+constexpr int kLuMaxTile = 1024;
+void launch_lu_panel(const LuPanelDesc& g, hipStream_t stream, double* ws, int prio = 0);
+size_t lu_panel_workspace_bytes();
+// the interchanges of a batch, one grouped launch per 48 descriptors
+void launch_laswp_batch(const LaswpDesc* descs, int n, hipStream_t stream, int prio = 0);
 void launch_trtri(const TrtriDesc& t, hipStream_t stream, double* ws);
 size_t trtri_workspace_bytes(const TrtriDesc& t);
 void launch_trmm_lt_batch(const TrmmDesc* descs, int n, hipStream_t stream);
@@ -377,6 +425,8 @@ struct KernelBatch {
   std::vector<TrsmLeftDesc> trsm_left;
   std::vector<PotrfDesc> potrf;
   std::vector<GetrfDesc> getrf;
+  std::vector<LuPanelDesc> lu_panel;
+  std::vector<LaswpDesc> laswp;  // launched before trsm_left (GESSM / SSSSM: interchange, solve, update)
   std::vector<TrtriDesc> trtri;
   std::vector<TrmmDesc> trmm;
   std::vector<LauumDesc> lauum;
@@ -392,8 +442,8 @@ struct KernelBatch {
   // (kernels: g_crit_cu, bulk_yield) so the chain runs at idle speed
   int claim_cus = 0;  // 1: tile-POTRF steps claim, 2: every kernel of the launch
   bool bulk_yield = false;  // bulk launch: poll the claims
-  bool empty() const { return pre_gemm.empty() && gemm.empty() && trsm.empty() && trsm_left.empty() && potrf.empty() && getrf.empty() && trtri.empty() && trmm.empty() && lauum.empty() && trsm_w.empty() && stencil.empty() && qr_panel.empty() && qr_apply.empty() && generic.empty(); }
-  void clear() { pre_gemm.clear(); gemm.clear(); trsm.clear(); trsm_left.clear(); potrf.clear(); getrf.clear(); trtri.clear(); trmm.clear(); lauum.clear(); trsm_w.clear(); stencil.clear(); qr_panel.clear(); qr_apply.clear(); generic.clear(); }
+  bool empty() const { return pre_gemm.empty() && gemm.empty() && trsm.empty() && trsm_left.empty() && potrf.empty() && getrf.empty() && lu_panel.empty() && laswp.empty() && trtri.empty() && trmm.empty() && lauum.empty() && trsm_w.empty() && stencil.empty() && qr_panel.empty() && qr_apply.empty() && generic.empty(); }
+  void clear() { pre_gemm.clear(); gemm.clear(); trsm.clear(); trsm_left.clear(); potrf.clear(); getrf.clear(); lu_panel.clear(); laswp.clear(); trtri.clear(); trmm.clear(); lauum.clear(); trsm_w.clear(); stencil.clear(); qr_panel.clear(); qr_apply.clear(); generic.clear(); }
 };
 
 struct HipDevice;

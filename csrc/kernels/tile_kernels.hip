@@ -3515,6 +3515,7 @@ size_t kernel_batch_workspace_bytes(const KernelBatch& b) {
   size_t w = 0;
   for (auto& p : b.potrf) w = std::max(w, kern::potrf_steps_eligible(p) ? kern::potrf_steps_workspace_bytes(p) : kern::potrf_workspace_bytes(p));
   for (auto& g : b.getrf) w = std::max(w, kern::getrf_workspace_bytes(g));
+  if (!b.lu_panel.empty()) w = std::max(w, kern::lu_panel_workspace_bytes());
   for (auto& t : b.trtri) w = std::max(w, kern::trtri_workspace_bytes(t));
   for (auto& l : b.lauum) w = std::max(w, kern::lauum_workspace_bytes(l));
   if (!b.trsm_w.empty()) w = std::max(w, kern::trsm_w_workspace_bytes(b.trsm_w.data(), (int)b.trsm_w.size()));
@@ -3549,9 +3550,12 @@ void launch_kernel_batch(KernelBatch& b, hipStream_t stream, int device_ordinal,
     else kern::launch_potrf(p, stream, static_cast<double*>(ws));
   }
   for (auto& g : b.getrf) kern::launch_getrf_nopiv(g, stream, static_cast<double*>(ws));
+  for (auto& g : b.lu_panel) kern::launch_lu_panel(g, stream, static_cast<double*>(ws), kern::t_launch_prio);
   if (!b.qr_panel.empty()) kern::launch_qr_panel_blocked(b.qr_panel.data(), (int)b.qr_panel.size(), stream, static_cast<double*>(ws));
   if (!b.trsm.empty()) kern::launch_trsm_batch(b.trsm.data(), (int)b.trsm.size(), stream, static_cast<double*>(ws));
   if (!b.trsm_w.empty()) kern::launch_trsm_w_batch(b.trsm_w.data(), (int)b.trsm_w.size(), stream, static_cast<double*>(ws));
+  // GESSM / SSSSM: the interchanges, then the unit lower solves; their updates are GEMMs
+  if (!b.laswp.empty()) kern::launch_laswp_batch(b.laswp.data(), (int)b.laswp.size(), stream, kern::t_launch_prio);
   if (!b.trsm_left.empty()) kern::launch_trsm_left_batch(b.trsm_left.data(), (int)b.trsm_left.size(), stream, static_cast<double*>(ws));
   if (!b.qr_apply.empty()) kern::launch_qr_apply(b.qr_apply.data(), (int)b.qr_apply.size(), stream, static_cast<double*>(ws));
   // the inverse kernels (DTRTRI / DLAUUM): a round's TRMMs are one grouped launch

@@ -36,6 +36,9 @@ extern "C" int parsec_amd_potrf_stamps(long long* out);
 extern "C" int parsec_amd_dtrsm_batch(const TrsmDesc* descs, int n, void* stream);
 extern "C" int parsec_amd_dtrsm_left_batch(const TrsmLeftDesc* descs, int n, void* stream);
 extern "C" int parsec_amd_dgetrf_nopiv_tile(double* A, int n, int lda, int* info, double* invL, double* invU, void* stream);
+extern "C" int parsec_amd_dgetrf_piv_tile(double* A, int n, int lda, double* L, int ldl, int* info, void* stream);
+extern "C" int parsec_amd_dtstrf_tile(double* U, int ldu, double* A2, int lda2, int h, int n, double* L, int ldl, int* info, void* stream);
+extern "C" int parsec_amd_dlaswp_pair(double* top, int ldt, int mt, double* bot, int ldb, int h, int ncols, const double* piv, int npiv, void* stream);
 extern "C" int parsec_amd_dtrtri_tile(double* A, int n, int lda, int* info, int info_base, double* W, int ldw, void* stream);
 extern "C" int parsec_amd_dtrmm_lt_batch(const parsec::TrmmDesc* descs, int n, void* stream);
 extern "C" int parsec_amd_dlauum_tile(double* A, int n, int lda, void* stream);
@@ -602,6 +605,19 @@ PYBIND11_MODULE(_C, m) {
   m.def("dgesv_nopiv_new", [](TiledMatrix* A, TiledMatrix* B) { return with_info_word([&](int* info) { return algos::dgesv_nopiv_new(A, B, info); }, composed); },
       py::arg("A"), py::arg("B"),
       "LU without pivoting then solve (one rank); returns (taskpool, info address) or None. When info != 0 the solve does not run and B is untouched");
+  m.def("dgetrf_incpiv_new", [](TiledMatrix* A, TiledMatrix* L) { return with_info_word([&](int* info) { return algos::dgetrf_incpiv_new(A, L, info); }, owned); },
+      py::arg("A"), py::arg("L"),
+      "tiled LU with incremental (pairwise) pivoting (square A, square tiles of at most 1024) from the ptgpp-compiled dgetrf_incpiv.jdf; L is a companion "
+      "collection tiled and distributed like A that receives the unit lower triangles and, in the last column of each tile, the pivots. Returns (taskpool, "
+      "info address) or None. info is the 1-based index of the first diagonal entry of U that is exactly zero");
+  m.def("dgetrs_incpiv_new", [](int trans, TiledMatrix* A, TiledMatrix* L, TiledMatrix* B) { return algos::dgetrs_incpiv_new(trans, A, L, B); }, py::arg("trans"),
+        py::arg("A"), py::arg("L"), py::arg("B"), py::return_value_policy::reference,
+        "solve A X = B with the factor of dgetrf_incpiv_new in A and L (MATRIX_NOTRANS only); B.mb must equal A.nb; None on invalid arguments. Release with "
+        "taskpool_free");
+  m.def("dgesv_incpiv_new", [](TiledMatrix* A, TiledMatrix* L, TiledMatrix* B) {
+        return with_info_word([&](int* info) { return algos::dgesv_incpiv_new(A, L, B, info); }, composed);
+      }, py::arg("A"), py::arg("L"), py::arg("B"),
+      "LU with incremental pivoting then solve (one rank); returns (taskpool, info address) or None. When info != 0 the solve does not run and B is untouched");
   m.def("dormqr_new", [](int side, int trans, TiledMatrix* A, TiledMatrix* T, TiledMatrix* B) { return (Taskpool*)algos::dormqr_new(side, trans, A, T, B); },
         py::arg("side"), py::arg("trans"), py::arg("A"), py::arg("T"), py::arg("B"), py::return_value_policy::reference,
         "B := op(Q) B with the Q of dgeqrf_jdf_new / dgeqrf_new (not dgeqrf_hqr_new) in A and T: MATRIX_LEFT, MATRIX_TRANS or MATRIX_NOTRANS; B.mb must equal "
@@ -885,6 +901,25 @@ PYBIND11_MODULE(_C, m) {
   }, py::arg("A"), py::arg("n"), py::arg("lda"), py::arg("info") = 0, py::arg("invL") = 0, py::arg("invU") = 0, py::arg("stream") = 0,
      "tile LU without pivoting on the GPU: the n x n column-major tile A := L\\U (L unit lower); info (device int, optional) receives the 1-based index of the "
      "first zero pivot; invL / invU (optional, ceil(n/64) x 4096 doubles) the inverses of the 64 x 64 diagonal blocks of L and U");
+  m.def("kernel_dgetrf_piv", [](uintptr_t A, int n, int lda, uintptr_t L, int ldl, uintptr_t info, uintptr_t stream) {
+    return parsec_amd_dgetrf_piv_tile((double*)A, n, lda, (double*)L, ldl, (int*)info, (void*)stream);
+  }, py::arg("A"), py::arg("n"), py::arg("lda"), py::arg("L"), py::arg("ldl"), py::arg("info") = 0, py::arg("stream") = 0,
+     "tile LU with partial pivoting on the GPU (n <= 1024): the n x n column-major tile A := L\\U as DGETRF leaves it; the strict lower triangle of L (ld ldl) "
+     "receives a copy of the multipliers and rows 0 .. n-1 of its column n-1 the pivots (1-based LAPACK ipiv values as doubles). A column of zeros keeps its "
+     "row and divides nothing; info (device int, optional) receives its 1-based index (the smallest wins)");
+  m.def("kernel_dtstrf", [](uintptr_t U, int ldu, uintptr_t A2, int lda2, int h, int n, uintptr_t L, int ldl, uintptr_t info, uintptr_t stream) {
+    return parsec_amd_dtstrf_tile((double*)U, ldu, (double*)A2, lda2, h, n, (double*)L, ldl, (int*)info, (void*)stream);
+  }, py::arg("U"), py::arg("ldu"), py::arg("A2"), py::arg("lda2"), py::arg("h"), py::arg("n"), py::arg("L"), py::arg("ldl"), py::arg("info") = 0,
+     py::arg("stream") = 0,
+     "pivoted LU of the stacked pair [U (n x n upper); A2 (h x n)] on the GPU (n, h <= 1024): P S = [L1; L2] U' with U' into U's upper triangle (its strict "
+     "lower triangle is not touched), L2 into A2, L1 into the strict lower triangle of L and the pivots (1 .. n a row of U, n+1 .. n+h a row of A2) into rows "
+     "0 .. n-1 of its column n-1; info as for kernel_dgetrf_piv");
+  m.def("kernel_dlaswp_pair", [](uintptr_t top, int ldt, int mt, uintptr_t bot, int ldb, int h, int ncols, uintptr_t piv, int npiv, uintptr_t stream) {
+    return parsec_amd_dlaswp_pair((double*)top, ldt, mt, (double*)bot, ldb, h, ncols, (const double*)piv, npiv, (void*)stream);
+  }, py::arg("top"), py::arg("ldt"), py::arg("mt"), py::arg("bot"), py::arg("ldb"), py::arg("h"), py::arg("ncols"), py::arg("piv"), py::arg("npiv"),
+     py::arg("stream") = 0,
+     "row interchanges of the stacked pair [top (mt rows); bot (h rows, 0 = none)] over ncols columns on the GPU: for j = 0 .. npiv-1 in sequence row j of top is "
+     "exchanged with row piv[j] (doubles; 1 .. mt in top, mt+1 .. mt+h in bot); an entry outside that range means no interchange");
   m.def("kernel_dtrtri", [](uintptr_t A, int n, int lda, uintptr_t info, int info_base, uintptr_t W, int ldw, uintptr_t stream) {
     return parsec_amd_dtrtri_tile((double*)A, n, lda, (int*)info, info_base, (double*)W, ldw, (void*)stream);
   }, py::arg("A"), py::arg("n"), py::arg("lda"), py::arg("info") = 0, py::arg("info_base") = 0, py::arg("W") = 0, py::arg("ldw") = 0, py::arg("stream") = 0,

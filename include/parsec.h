@@ -708,6 +708,33 @@ parsec_taskpool_t* parsec_dgels_New(parsec_tiled_matrix_t* A, parsec_tiled_matri
 parsec_taskpool_t* parsec_dgetrf_nopiv_New(parsec_tiled_matrix_t* A, int* info);
 parsec_taskpool_t* parsec_dgetrs_nopiv_New(parsec_matrix_trans_t trans, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B);
 parsec_taskpool_t* parsec_dgesv_nopiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* B, int* info);
+/* LU with incremental (pairwise) pivoting of a square double matrix with square
+ * tiles of at most 1024 (a ragged last tile is allowed; the ptgpp-compiled
+ * dgetrf_incpiv.jdf and dgetrs_incpiv.jdf, DPLASMA's dplasma_dgetrf_incpiv_New
+ * / dgetrs_incpiv / dgesv_incpiv roles): safe on matrices that need pivoting.
+ * L is a companion collection of the same type, tile size (nb x nb), tile grid
+ * and distribution as A; its contents on entry do not matter. On return A holds
+ * U and, below the diagonal tiles, the multipliers L2 of each tile pair; tile
+ * (m, k), m >= k, of L holds in its strict lower triangle a unit lower
+ * triangle (k == m: a clean copy of the L of A(k,k); m > k: the L1 of the pair
+ * [U(k,k); A(m,k)], a full triangle) and in rows 0 .. nb-1 of its last column
+ * (column nb-1 of the nb x nb allocation) the pivots: LAPACK ipiv values stored
+ * as doubles, 1-based and applied in sequence, counted over the stacked rows of
+ * the pair (1 .. nb a row of the top tile, nb+1 .. nb+h a row of the bottom
+ * tile). A column whose candidates are all exactly zero keeps its row and
+ * divides nothing, so a zero pivot never puts inf / nan into the factor; *info
+ * holds the 1-based global index of the first diagonal entry of U that is
+ * exactly zero once the taskpool completed (0: none).
+ * parsec_dgetrs_incpiv_New: A X = B with that factor, PARSEC_MATRIX_NOTRANS
+ * only; B is N x NRHS with B->mb == A->nb, on any process grid.
+ * parsec_dgesv_incpiv_New: factor then solve in one taskpool; with *info != 0
+ * the solve does not run and B is untouched; info is required; one rank only.
+ * Pairwise pivoting is weaker than partial pivoting: the error grows with the
+ * number of tile rows. All return NULL (after a warning) for any other request
+ * or shape; release the two composed ones with parsec_taskpool_free. */
+parsec_taskpool_t* parsec_dgetrf_incpiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* L, int* info);
+parsec_taskpool_t* parsec_dgetrs_incpiv_New(parsec_matrix_trans_t trans, parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* L, parsec_tiled_matrix_t* B);
+parsec_taskpool_t* parsec_dgesv_incpiv_New(parsec_tiled_matrix_t* A, parsec_tiled_matrix_t* L, parsec_tiled_matrix_t* B, int* info);
 /* The inverse with the Cholesky factor (DPLASMA's dplasma_dtrtri_New /
  * dlauum / dpotri / dpoinv roles; the ptgpp-compiled dtrtri_L.jdf and
  * dlauum_L.jdf) of a square double matrix with square tiles (a ragged last tile

@@ -62,6 +62,7 @@ CORE_SOURCES = [
 HIP_SOURCES = [
     "csrc/kernels/tile_kernels.hip",
     "csrc/kernels/qr_kernels.hip",
+    "csrc/kernels/lu_kernels.hip",
     "csrc/kernels/stencil_kernels.hip",
 ]
 PY_SOURCES = ["csrc/python/bindings.cpp"]
@@ -73,6 +74,8 @@ JDF_SOURCES = [
     "csrc/algos/jdf/dgeqrf.jdf",
     "csrc/algos/jdf/dtrsm_left.jdf",
     "csrc/algos/jdf/dgetrf_nopiv.jdf",
+    "csrc/algos/jdf/dgetrf_incpiv.jdf",
+    "csrc/algos/jdf/dgetrs_incpiv.jdf",
     "csrc/algos/jdf/dtrtri_L.jdf",
     "csrc/algos/jdf/dlauum_L.jdf",
     "csrc/algos/jdf/dormqr.jdf",
@@ -279,7 +282,7 @@ def generate_sanitized(kind):
     # Cholesky (ptgpp-compiled dpotrf_L.jdf, CPU bodies on 1..4 ranks); the
     # factor-and-solve program (dtrsm_left.jdf) is built beside them
     for capi in ("tests/capi/dtd_capi.c", "tests/capi/dpotrf_capi.c", "tests/capi/dpotrs_capi.c", "tests/capi/dgels_capi.c",
-                 "tests/capi/dgetrf_capi.c", "tests/capi/dpotri_capi.c"):
+                 "tests/capi/dgetrf_capi.c", "tests/capi/dgetrf_incpiv_capi.c", "tests/capi/dpotri_capi.c"):
         if not os.path.exists(os.path.join(ROOT, capi)):
             continue
         name = os.path.splitext(os.path.basename(capi))[0]
