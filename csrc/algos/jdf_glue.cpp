@@ -4,6 +4,7 @@
 #include <vector>
 
 #include "../device/device.hpp"
+#include "../kernels/kernels.hpp"
 
 namespace parsec {
 namespace algos {

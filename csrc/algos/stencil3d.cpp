@@ -21,15 +21,11 @@
 #include <cstring>
 
 #include "../device/device.hpp"
+#include "../kernels/kernels.hpp"
 #include "../comm/comm.hpp"
 #include "../dtd/dtd.hpp"
 
 namespace parsec {
-namespace kern {
-using StencilArgs = StencilDesc;
-void launch_stencil_init(const StencilInitDesc& d, hipStream_t stream);
-}  // namespace kern
-
 namespace algos {
 
 // ------------------------------------------------------------- collection

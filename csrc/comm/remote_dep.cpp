@@ -22,6 +22,7 @@
 #include <unordered_map>
 
 #include "../device/device.hpp"
+#include "../kernels/kernels.hpp"
 #include "../prof/profiling.hpp"
 #include "fetch_queue.hpp"
 #include "shm_engine.hpp"

@@ -81,8 +81,8 @@ void cpu_stage_in(ExecutionStream* es, Task* t);
 void cpu_write_epilog(Task* t);
 
 // ------------------------------------------------------------------ batching
-// Kernel kinds that a GPU chore can enqueue into the manager's per-round batch.
-enum BatchKind : int { BATCH_GEMM = 0, BATCH_TRSM, BATCH_POTRF, BATCH_GEQRT, BATCH_TSQRT, BATCH_UNMQR, BATCH_TSMQR, BATCH_STENCIL, BATCH_NB_KINDS };
+// Descriptors that a GPU chore enqueues into the manager's per-round batch
+// (KernelBatch below). The launchers that take them: kernels/kernels.hpp.
 
 struct GemmDesc {
   const double* A;
@@ -262,109 +262,13 @@ struct TrsmGemmDesc {
   int m, n;  // B is m x n, W is n x n lower triangular
   int ldb, ldw;
   // optional: the factor itself, for the substitution fallback of
-  // PARSEC_DPOTRF_TRSM=auto / blocked (trsm_inverse_mode)
+  // PARSEC_DPOTRF_TRSM=auto / blocked (kernels/kernels.hpp trsm_inverse_mode)
   const double* L = nullptr;
   int ldl = 0;
   // 1: W is a packed panel tile (PotrfDesc::pack_w): W below and on the
   // diagonal, L^T above; L = W, ldl = ldw
   uint8_t packed = 0;
 };
-
-// Panel solve of the tile Cholesky: 0 = always through W = L^-1, 1 = auto (W
-// unless max|L| * max|W| > limit, then blocked substitution), 2 = always
-// blocked substitution. Returns the previous mode; limit <= 0 keeps it.
-int trsm_inverse_mode(int mode, double limit);
-double trsm_inverse_limit();
-namespace kern {
-// Inverses of the 64 x 64 diagonal blocks of L (n x n lower, ld ldl) into invD:
-// block b at invD + b * 4096, column-major, padded with the identity
-// (unit: L's diagonal is taken as 1 and never read)
-void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream, bool unit = false);
-// the same for U (n x n upper): the blocks of invD are upper triangular; U's
-// strict lower triangle is never read
-void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipStream_t stream, bool unit = false);
-// tile LU without pivoting; ws: getrf_workspace_bytes(g)
-void launch_getrf_nopiv(const GetrfDesc& g, hipStream_t stream, double* ws);
-size_t getrf_workspace_bytes(const GetrfDesc& g);
-// tile TRTRI / grouped TRMM (B := alpha L^T B) / tile LAUUM; ws: *_workspace_bytes
-// tile / stacked-pair LU with partial pivoting (lu_kernels.hip); ws:
-// lu_panel_workspace_bytes(). prio: raise the waves' issue priority
-constexpr int kLuMaxTile = 1024;
-void launch_lu_panel(const LuPanelDesc& g, hipStream_t stream, double* ws, int prio = 0);
-size_t lu_panel_workspace_bytes();
-// the interchanges of a batch, one grouped launch per 48 descriptors
-void launch_laswp_batch(const LaswpDesc* descs, int n, hipStream_t stream, int prio = 0);
-void launch_trtri(const TrtriDesc& t, hipStream_t stream, double* ws);
-size_t trtri_workspace_bytes(const TrtriDesc& t);
-void launch_trmm_lt_batch(const TrmmDesc* descs, int n, hipStream_t stream);
-void launch_lauum(const LauumDesc& l, hipStream_t stream, double* ws);
-size_t lauum_workspace_bytes(const LauumDesc& l);
-// Vout (rows x min(rows, cols), ld rows) := the unit-lower V stored below the
-// diagonal of a factored QR diagonal tile A (ld lda): ones on the diagonal,
-// zeros above (the layout of QrPanelDesc::Vcopy)
-void launch_qr_extract_v(const double* A, int lda, int rows, int cols, double* Vout, hipStream_t stream);
-// device_hip_cu_yield as the kernels see it (QR sub-panel kernels claim their CUs when > 0)
-void set_cu_yield_mode(int m);
-int cu_yield_mode();
-// auto panel solve: 1 = the TRSM launch decides from the estimate the local
-// POTRF published to pinned host memory (default), 0 = always the device-side
-// gate; < 0 queries. Returns the previous setting.
-int trsm_estimate_route(int on);
-// [0] estimates published by tile POTRFs, [1] panel decisions taken on the
-// host, [2] panels left to the device-side gate
-void trsm_estimate_stats(uint64_t out[3], bool reset);
-// a device buffer was (re)allocated: drop a panel estimate keyed by its address
-void trsm_estimate_forget(const void* p);
-double trsm_estimate_lookup(const void* p);
-std::vector<uintptr_t> trsm_estimate_known();
-// What the host decides for one grouped-DGEMM launch: the tile shape, the
-// operand mode, the tile / workgroup counts and the kernel. The launch is
-// issued from this record, and the launch log keeps it.
-struct GemmLaunchRecord {
-  int bm, bn;
-  int descs;        // descriptors of the launch
-  int total_tiles;  // tiles of all descriptors
-  int main_tiles;   // tiles run whole; the other total_tiles - main_tiles are split ksplit ways along K
-  int ksplit;
-  int grid;         // workgroups
-  int pad_bytes;    // extra dynamic LDS (one bulk workgroup per CU)
-  uint8_t transA, transB;
-  uint8_t full;     // unchecked loads
-  uint8_t epilogue; // 0 plain (C preload when |alpha| = 1), 1 atomic
-  uint8_t rotated;  // rotated k loop (gemm_mainloop)
-  uint8_t pipelined; // rotated loop with the pinned body (gemm_pipeline)
-};
-// The launches launch_gemm_batch would issue for these descriptors on `slots`
-// resident 128 x 128 workgroups under the current policy settings, in order,
-// to out (room for n); returns their number. one_per_cu: a padded bulk launch
-// (half the slots), bulk_yield / claim: as a yielding bulk stream or a
-// claiming critical stream (claim >= 2) launches. Host code only: no device is
-// touched and no descriptor pointer is dereferenced.
-int gemm_launch_plan(const GemmDesc* descs, int n, int slots, bool one_per_cu, bool bulk_yield, int claim, GemmLaunchRecord* out);
-constexpr int kGemmLaunchLogSize = 64;
-// Per-thread record of the last kGemmLaunchLogSize grouped-DGEMM launches,
-// written only while switched on: on 1 / 0, < 0 queries; returns the previous setting.
-int gemm_launch_log(int on);
-// Copies the calling thread's records, oldest first, to out (room for
-// kGemmLaunchLogSize) and returns their number; reset empties the record.
-int gemm_launch_log_read(GemmLaunchRecord* out, bool reset);
-// Round-filling launch chunks on (1) / off (0: fixed launches of 40 descriptors), < 0 queries; returns the previous setting.
-int gemm_chunk_fill(int on);
-// The launch chunks launch_gemm_batch cuts for count descriptors of one operand
-// mode with C of m[i] x n[i], on `slots` resident 128 x 128 workgroups: their
-// lengths go to out (room for count), their number is returned. Host code only.
-int gemm_chunk_plan(const int* m, const int* n, int count, int slots, int* out);
-// Body of the rotated k loop, consulted only when gemm_mainloop is 1: 0 = the
-// compiler's order inside a k-tile, 1 = the pinned order (fragment reads a
-// kk-group of MFMAs ahead of their use), < 0 queries; returns the previous setting.
-int gemm_pipeline(int mode);
-// Whether a bm x bn x bk tile launch may take the pinned body for a descriptor
-// with these transposes and leading dimensions: its per-thread operand offsets
-// are 32-bit byte offsets, which span bk columns of A (bm of a transposed A)
-// and bn columns of B (bk of a transposed B); 0 keeps the compiler-scheduled
-// body. Host code only.
-int gemm_pipeline_fits(int bm, int bn, int bk, int transA, int transB, long long lda, long long ldb);
-}  // namespace kern
 
 // Householder QR of a tile (GEQRT: A2 == nullptr) or of a triangle on top of a
 // tile (TSQRT: [R = A1 (upper); A2]), compact WY with a full n x n upper T.
@@ -442,8 +346,20 @@ struct KernelBatch {
   // (kernels: g_crit_cu, bulk_yield) so the chain runs at idle speed
   int claim_cus = 0;  // 1: tile-POTRF steps claim, 2: every kernel of the launch
   bool bulk_yield = false;  // bulk launch: poll the claims
-  bool empty() const { return pre_gemm.empty() && gemm.empty() && trsm.empty() && trsm_left.empty() && potrf.empty() && getrf.empty() && lu_panel.empty() && laswp.empty() && trtri.empty() && trmm.empty() && lauum.empty() && trsm_w.empty() && stencil.empty() && qr_panel.empty() && qr_apply.empty() && generic.empty(); }
-  void clear() { pre_gemm.clear(); gemm.clear(); trsm.clear(); trsm_left.clear(); potrf.clear(); getrf.clear(); lu_panel.clear(); laswp.clear(); trtri.clear(); trmm.clear(); lauum.clear(); trsm_w.clear(); stencil.clear(); qr_panel.clear(); qr_apply.clear(); generic.clear(); }
+  // every queue, once: a new queue is listed here and nowhere else
+  template <class Self, class F>
+  static void each_queue(Self& b, F&& f) {
+    f(b.pre_gemm); f(b.gemm); f(b.trsm); f(b.trsm_left); f(b.potrf); f(b.getrf); f(b.lu_panel); f(b.laswp);
+    f(b.trtri); f(b.trmm); f(b.lauum); f(b.trsm_w); f(b.stencil); f(b.qr_panel); f(b.qr_apply); f(b.generic);
+  }
+  bool empty() const {
+    bool none = true;
+    each_queue(*this, [&](const auto& q) { none = none && q.empty(); });
+    return none;
+  }
+  void clear() {
+    each_queue(*this, [](auto& q) { q.clear(); });
+  }
 };
 
 struct HipDevice;
@@ -468,8 +384,8 @@ struct GpuExecContext {
 
 using GpuHook = std::function<int(GpuExecContext*, Task*)>;
 
-// Flush a batch on a stream (implemented next to the kernels).
-void launch_kernel_batch(KernelBatch& b, hipStream_t stream, int device_ordinal, void* workspace);
+// Flush a batch on a stream (kernels/kernel_batch.cpp).
+void launch_kernel_batch(KernelBatch& b, hipStream_t stream, void* workspace);
 size_t kernel_batch_workspace_bytes(const KernelBatch& b);
 
 }  // namespace parsec

@@ -11,6 +11,7 @@
 
 #include <rocprofiler-sdk-roctx/roctx.h>
 
+#include "../kernels/kernels.hpp"
 #include "../prof/profiling.hpp"
 
 namespace parsec {
@@ -1213,7 +1214,7 @@ void HipDevice::execute_ready() {
     int rc = ch.gpu_hook ? ch.gpu_hook(&ctxg, t) : HOOK_NEXT;
     PARSEC_PINS(es, PINS_EXEC_END, t);
     if (!batching && !local_batch.empty()) {
-      launch_kernel_batch(local_batch, s_exec[s], ordinal, workspace(s, kernel_batch_workspace_bytes(local_batch) + 64));
+      launch_kernel_batch(local_batch, s_exec[s], workspace(s, kernel_batch_workspace_bytes(local_batch) + 64));
       stats.kernel_launches.fetch_add(1, std::memory_order_relaxed);
     }
     if (rc == HOOK_DONE) {
@@ -1262,7 +1263,7 @@ void HipDevice::launch_group(int s) {
       std::snprintf(label, sizeof(label), "%s s%d n%zu %s", name.c_str(), s, round_tasks[s].size(), t0->task_class->name.c_str());
       roctxRangePushA(label);
     }
-    launch_kernel_batch(batches[s], s_exec[s], ordinal, workspace(s, kernel_batch_workspace_bytes(batches[s]) + 64));
+    launch_kernel_batch(batches[s], s_exec[s], workspace(s, kernel_batch_workspace_bytes(batches[s]) + 64));
     if (roctx) roctxRangePop();
     stats.kernel_launches.fetch_add(1, std::memory_order_relaxed);
     batches[s].clear();

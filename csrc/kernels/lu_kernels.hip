@@ -1,8 +1,9 @@
-// CDNA4 (gfx950) kernels of the tile LU with incremental (pairwise) pivoting
+// CDNA4 (gfx950) kernels of the tile LU: without pivoting (dgetrf_nopiv.jdf,
+// the second half of this file) and with incremental (pairwise) pivoting
 // (dgetrf_incpiv.jdf / dgetrs_incpiv.jdf): the pivoted factorization of a tile
 // (GETRF) or of an upper triangle stacked on a tile (TSTRF), and the grouped row
 // interchanges of GESSM / SSSSM. The solves and updates of those tasks are the
-// left-side tile solve and the grouped DGEMM of tile_kernels.hip.
+// left-side tile solve of trsm_kernels.hip and the grouped DGEMM of tile_kernels.hip.
 //
 // Factorization, blocked by 64 columns. Per strip j (w <= 64 columns):
 //   dlu_strip_kernel     ONE workgroup factors the strip with partial pivoting.
@@ -36,13 +37,12 @@
 #include <type_traits>
 #include <utility>
 
-#include "../device/device.hpp"
+#include "device_helpers.hpp"
+#include "kernels.hpp"
+#include "launch_settings.hpp"
 
 namespace parsec {
 namespace kern {
-
-void launch_gemm_batch(const GemmDesc* descs, int n, hipStream_t stream);                             // tile_kernels.hip
-void launch_trsm_left_batch(const TrsmLeftDesc* descs, int n, hipStream_t stream, double* ws);        // tile_kernels.hip
 
 constexpr int kLuThreads = 256;
 constexpr int kLuSub = 16;
@@ -279,12 +279,12 @@ __global__ __launch_bounds__(64) void dlaswp_pair_kernel(const LaswpArgs a) {
   }
 }
 
-void launch_laswp_batch(const LaswpDesc* descs, int n, hipStream_t stream, int prio) {
+void launch_laswp_batch(const LaswpDesc* descs, int n, hipStream_t stream) {
   for (int s0 = 0; s0 < n; s0 += kMaxLaswpBatch) {
     const int cnt = std::min(kMaxLaswpBatch, n - s0);
     LaswpArgs a;
     a.count = cnt;
-    a.prio = prio;
+    a.prio = launch_settings().prio;
     int total = 0;
     for (int i = 0; i < cnt; ++i) {
       a.d[i] = descs[s0 + i];
@@ -308,7 +308,7 @@ __global__ __launch_bounds__(256) void lu_copy_strict_lower_kernel(const double*
 
 size_t lu_panel_workspace_bytes() { return 4096 * sizeof(double); }  // the inverse of one 64 x 64 unit lower block
 
-void launch_lu_panel(const LuPanelDesc& g, hipStream_t stream, double* ws, int prio) {
+void launch_lu_panel(const LuPanelDesc& g, hipStream_t stream, double* ws) {
   const int n = g.n;
   if (n <= 0) return;
   const bool ts = g.B != nullptr;
@@ -333,7 +333,7 @@ void launch_lu_panel(const LuPanelDesc& g, hipStream_t stream, double* ws, int p
     a.piv_top = j;
     a.piv_bot = ts ? n : j + w;
     a.info_base = g.info_base + j;
-    a.prio = prio;
+    a.prio = launch_settings().prio;
     const int rows = a.w + a.hb;
     if (rows <= kLuThreads) hipLaunchKernelGGL(dlu_strip_kernel<1>, dim3(1), dim3(kLuThreads), 0, stream, a);
     else if (rows <= 2 * kLuThreads) hipLaunchKernelGGL(dlu_strip_kernel<2>, dim3(1), dim3(kLuThreads), 0, stream, a);
@@ -345,7 +345,7 @@ void launch_lu_panel(const LuPanelDesc& g, hipStream_t stream, double* ws, int p
     if (j > 0) sw[ns++] = LaswpDesc{ts ? g.L : g.T, ts ? g.B : nullptr, piv, ts ? g.ldl : g.ldt, g.ldb, n, ts ? g.h : 0, j, j, j + w};
     if (rest > 0)
       sw[ns++] = LaswpDesc{g.T + (size_t)(j + w) * g.ldt, ts ? g.B + (size_t)(j + w) * g.ldb : nullptr, piv, g.ldt, g.ldb, n, ts ? g.h : 0, rest, j, j + w};
-    launch_laswp_batch(sw, ns, stream, prio);
+    launch_laswp_batch(sw, ns, stream);
     if (rest <= 0) break;
     double* urow = g.T + (size_t)(j + w) * g.ldt + j;  // the block row right of the strip
     TrsmLeftDesc t{a.Lp, urow, w, rest, a.ldl, g.ldt, 1.0, 0, 0, 1, 0, nullptr};
@@ -362,39 +362,194 @@ void launch_lu_panel(const LuPanelDesc& g, hipStream_t stream, double* ws, int p
   if (!ts && n > 1) hipLaunchKernelGGL(lu_copy_strict_lower_kernel, dim3(n - 1), dim3(256), 0, stream, (const double*)g.T, g.ldt, g.L, g.ldl, n);
 }
 
+// ================================== tile GETRF without pivoting (A = L U)
+// Right-looking, blocked by 64 columns, three launches per block column j:
+//   dgetrf_diag_kernel   one workgroup: A_jj := L_jj \ U_jj in registers, then
+//                        inv(L_jj) (unit lower) and inv(U_jj) the same way
+//   dgetrf_panel_kernel  one workgroup per 64 x 64 block of the block column
+//                        below (A_ij := A_ij inv(U_jj)) and of the block row to
+//                        the right (A_jk := inv(L_jj) A_jk): one 64^3 product on
+//                        v_mfma_f64_16x16x4f64 from LDS
+//   the grouped NN GEMM  A_ik -= A_ij A_jk over the trailing part
+// No pivoting: a zero pivot is reported and the factorization goes on with
+// inf / nan. 50 KB (diagonal) and 75 KB (panel) of LDS: either fits beside one
+// resident 128 x 128 GEMM workgroup.
+constexpr int kGetrfLd = 65;   // F of the diagonal kernel: [column][row], one pad
+constexpr int kGetrfLdA = 80;  // MFMA A operand [k][row]: the two k of a 32-lane half land 32 banks apart
+constexpr int kGetrfLdB = 66;  // MFMA B operand [column][k]: 16 columns x 2 k on 32 distinct bank pairs
+
+__global__ __launch_bounds__(256) void dgetrf_diag_kernel(double* A, int lda, int j, int w, double* invL, double* invU, int* info, int info_base, int prio) {
+  __shared__ double F[64 * kGetrfLd];      // F[c][r] = (L\U)(r, c), identity-padded past w
+  __shared__ double Pn[2 * 16 * kGetrfLd];  // the two panel broadcast buffers
+  __shared__ double rcp[64];  // 1 / U(c, c)
+  __shared__ int bad_s;
+  PARSEC_WAVE_PRIO(prio);
+  double* T = A + (size_t)j * lda + j;
+  const int r = threadIdx.x & 63;
+  const int v = threadIdx.x >> 6;
+  // thread (r, v): row r, columns 16v .. 16v+15
+  double a[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = 16 * v + i;
+    a[i] = (r < w && c < w) ? T[(size_t)c * lda + r] : (r == c ? 1.0 : 0.0);
+  }
+  if (threadIdx.x == 0) bad_s = 0x7fffffff;
+  __syncthreads();
+#pragma unroll 1
+  for (int p = 0; p < 4; ++p) {
+    double* pn = Pn + (p & 1) * 16 * kGetrfLd;
+    if (v == p) {
+      // wave p factors its 64 x 16 panel: lane jc holds row jc of U
+      int bad = 0x7fffffff;
+#pragma unroll
+      for (int jj = 0; jj < 16; ++jj) {
+        const int jc = 16 * p + jj;
+        const double d = readlane_d(a[jj], jc);
+        if (d == 0.0 && bad == 0x7fffffff) bad = jc + 1;  // the padding's pivots are 1
+        const double rd = 1.0 / d;
+        if (r > jc) a[jj] *= rd;
+        const double lv = r > jc ? a[jj] : 0.0;
+#pragma unroll
+        for (int i = jj + 1; i < 16; ++i) a[i] = __builtin_fma(-lv, readlane_d(a[i], jc), a[i]);
+        if (r == jc) rcp[jc] = rd;
+      }
+      if (r == 0 && bad != 0x7fffffff) atomicMin(&bad_s, bad);
+#pragma unroll
+      for (int i = 0; i < 16; ++i) pn[i * kGetrfLd + r] = a[i];
+    }
+    __syncthreads();
+    if (v > p) {
+      // the columns to the right: row 16p+s of U is final once the rows above it
+      // were applied; every row below takes its multiple (solve and update in one)
+#pragma unroll
+      for (int s = 0; s < 16; ++s) {
+        const int js = 16 * p + s;
+        const double l = r > js ? pn[s * kGetrfLd + r] : 0.0;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) a[i] = __builtin_fma(-l, readlane_d(a[i], js), a[i]);
+      }
+    }
+  }
+  if (threadIdx.x == 0 && bad_s != 0x7fffffff && info) {
+    const int val = info_base + j + bad_s;
+    const int old = atomicCAS(info, 0, val);
+    if (old != 0 && val < old) atomicMin(info, val);
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = 16 * v + i;
+    if (r < w && c < w) T[(size_t)c * lda + r] = a[i];
+    F[c * kGetrfLd + r] = a[i];
+  }
+  __syncthreads();
+  // The inverses by the same elimination on the identity, again with a row per
+  // lane and 16 columns per wave: X = inv(L) from L X = I, and Y = inv(U)^T from
+  // U^T Y = I (U^T is lower, with U's diagonal). Row js of either is final when
+  // step js starts; the rows below take their multiple of it. Columns 16v.. of a
+  // row js < 16v are still zero, so wave v starts at js = 16v.
+  double x[16], y[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) x[i] = y[i] = (r == 16 * v + i) ? 1.0 : 0.0;
+#pragma unroll 1
+  for (int js = 16 * v; js < 64; ++js) {
+    const double l = r > js ? F[js * kGetrfLd + r] : 0.0;  // L(r, js)
+    const double u = r > js ? F[r * kGetrfLd + js] : 0.0;  // U(js, r) = U^T(r, js)
+    const double rd = rcp[js];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      x[i] = __builtin_fma(-l, readlane_d(x[i], js), x[i]);
+      const double yj = readlane_d(y[i], js) * rd;
+      y[i] = r == js ? yj : __builtin_fma(-u, yj, y[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int c = 16 * v + i;
+    if (invL) invL[(size_t)c * 64 + r] = x[i];  // inv(L)(r, c)
+    if (invU) invU[(size_t)r * 64 + c] = y[i];  // inv(U)(c, r) = Y(r, c)
+  }
+}
+
+// blockIdx.x < nrb: block i of the column panel, A_ij := A_ij inv(U_jj);
+// else block k of the row panel, A_jk := inv(L_jj) A_jk. The diagonal block is a
+// full 64 x 64 one (there is no panel after a ragged one).
+__global__ __launch_bounds__(256) void dgetrf_panel_kernel(double* A, int lda, int n, int j, const double* __restrict__ invL, const double* __restrict__ invU, int nrb, int prio) {
+  __shared__ double As[64 * kGetrfLdA];  // As[k][row]: the left factor of the product
+  __shared__ double Bs[64 * kGetrfLdB];  // Bs[column][k]: the right factor
+  PARSEC_WAVE_PRIO(prio);
+  const bool below = (int)blockIdx.x < nrb;
+  const int o = j + 64 + 64 * (below ? (int)blockIdx.x : (int)blockIdx.x - nrb);
+  const int wb = min(64, n - o);
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int fr = lane & 15, fk = lane >> 4;
+  // the block of A: rows r0.., columns c0.., mr x nc valid
+  const int r0 = below ? o : j, c0 = below ? j : o;
+  const int mr = below ? wb : 64, nc = below ? 64 : wb;
+  double* __restrict__ Ab = A + (size_t)c0 * lda + r0;
+  for (int idx = tid; idx < 4096; idx += 256) {
+    const int lo = idx & 63, hi = idx >> 6;
+    if (below) {
+      As[hi * kGetrfLdA + lo] = lo < mr ? Ab[(size_t)hi * lda + lo] : 0.0;  // A_ij(row lo, k hi)
+      Bs[hi * kGetrfLdB + lo] = invU[hi * 64 + lo];                         // inv(U)(k lo, column hi)
+    } else {
+      As[hi * kGetrfLdA + lo] = invL[hi * 64 + lo];                         // inv(L)(row lo, k hi)
+      Bs[hi * kGetrfLdB + lo] = hi < nc ? Ab[(size_t)hi * lda + lo] : 0.0;  // A_jk(k lo, column hi)
+    }
+  }
+  __syncthreads();
+  // wave wv: rows 16wv .. 16wv+15 of the product, four 16-column accumulators
+  double4_t acc[4];
+#pragma unroll
+  for (int u = 0; u < 4; ++u) acc[u] = (double4_t){0.0, 0.0, 0.0, 0.0};
+#pragma unroll 4
+  for (int kk = 0; kk < 64; kk += 4) {
+    const double av = As[(kk + fk) * kGetrfLdA + 16 * wv + fr];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Bs[(16 * u + fr) * kGetrfLdB + kk + fk], acc[u], 0, 0, 0);
+  }
+#pragma unroll
+  for (int u = 0; u < 4; ++u) {
+    const int c = 16 * u + fr;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int rr = 16 * wv + fk + 4 * q;
+      if (rr < mr && c < nc) Ab[(size_t)c * lda + rr] = acc[u][q];
+    }
+  }
+}
+
+size_t getrf_workspace_bytes(const GetrfDesc& g) {
+  const size_t nblk = (size_t)((g.n + 63) / 64);
+  return ((g.invL_out ? 0 : nblk) + (g.invU_out ? 0 : nblk)) * 4096 * sizeof(double);
+}
+
+void launch_getrf_nopiv(const GetrfDesc& g, hipStream_t stream, double* ws) {
+  if (g.n <= 0) return;
+  if (g.n > kTrsmMaxCols) fatal("dgetrf tile kernel: n=%d exceeds the tile limit %d", g.n, kTrsmMaxCols);
+  if (g.lda < g.n) fatal("dgetrf tile kernel: lda=%d < n=%d", g.lda, g.n);
+  const int nblk = (g.n + 63) / 64;
+  double* il = g.invL_out ? g.invL_out : ws;
+  double* iu = g.invU_out ? g.invU_out : ws + (g.invL_out ? 0 : (size_t)nblk * 4096);
+  for (int j = 0; j < g.n; j += 64) {
+    const int jb = std::min(64, g.n - j);
+    double* bl = il + (size_t)(j / 64) * 4096;
+    double* bu = iu + (size_t)(j / 64) * 4096;
+    hipLaunchKernelGGL(dgetrf_diag_kernel, dim3(1), dim3(256), 0, stream, g.A, g.lda, j, jb, bl, bu, g.info, g.info_base, launch_settings().prio);
+    const int rest = g.n - j - jb;
+    if (rest <= 0) break;
+    const int nrb = (rest + 63) / 64;
+    hipLaunchKernelGGL(dgetrf_panel_kernel, dim3(2 * nrb), dim3(256), 0, stream, g.A, g.lda, g.n, j, (const double*)bl, (const double*)bu, nrb, launch_settings().prio);
+    GemmDesc e{};
+    e.A = g.A + (size_t)j * g.lda + j + jb;
+    e.B = g.A + (size_t)(j + jb) * g.lda + j;
+    e.C = g.A + (size_t)(j + jb) * g.lda + j + jb;
+    e.m = rest; e.n = rest; e.k = jb;
+    e.lda = e.ldb = e.ldc = g.lda;
+    e.alpha = -1.0; e.beta = 1.0;
+    launch_gemm_batch(&e, 1, stream);
+  }
+}
+
 }  // namespace kern
 }  // namespace parsec
-
-// ------------------------------------------------- C entry points (tests)
-namespace {
-double* lu_test_ws() {
-  static double* ws = [] {
-    void* p = nullptr;
-    (void)hipMalloc(&p, parsec::kern::lu_panel_workspace_bytes() + 64);
-    return static_cast<double*>(p);
-  }();
-  return ws;
-}
-}  // namespace
-
-extern "C" {
-// Tile LU with partial pivoting: A (n x n) := L\U, the strict lower triangle of
-// L := that of the factor, rows 0 .. n-1 of column n-1 of L := the pivots
-int parsec_amd_dgetrf_piv_tile(double* A, int n, int lda, double* L, int ldl, int* info, void* stream) {
-  parsec::LuPanelDesc g{A, lda, nullptr, 0, 0, n, L, ldl, n - 1, info, 0};
-  parsec::kern::launch_lu_panel(g, (hipStream_t)stream, lu_test_ws());
-  return (int)hipGetLastError();
-}
-// Pivoted LU of [U (n x n upper); A2 (h x n)]; L as above with pivots 1 .. n + h
-int parsec_amd_dtstrf_tile(double* U, int ldu, double* A2, int lda2, int h, int n, double* L, int ldl, int* info, void* stream) {
-  parsec::LuPanelDesc g{U, ldu, A2, lda2, h, n, L, ldl, n - 1, info, 0};
-  parsec::kern::launch_lu_panel(g, (hipStream_t)stream, lu_test_ws());
-  return (int)hipGetLastError();
-}
-// The interchanges piv[0 .. npiv-1] on [top (mt rows); bot (h rows, may be null)], ncols columns
-int parsec_amd_dlaswp_pair(double* top, int ldt, int mt, double* bot, int ldb, int h, int ncols, const double* piv, int npiv, void* stream) {
-  parsec::LaswpDesc d{top, bot, piv, ldt, ldb, mt, h, ncols, 0, npiv};
-  parsec::kern::launch_laswp_batch(&d, 1, (hipStream_t)stream);
-  return (int)hipGetLastError();
-}
-}

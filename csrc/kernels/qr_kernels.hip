@@ -16,28 +16,22 @@
 #include <cstdlib>
 #include <vector>
 
-#include "../device/device.hpp"
+#include "device_helpers.hpp"
+#include "kernels.hpp"
 
 namespace parsec {
 namespace kern {
 // Cooperative CU claim (device_hip_cu_yield, tile_kernels.hip g_crit_cu): the
 // TS chain's sub-panel kernels count themselves into the per-CU table so bulk
 // GEMM workgroups on their CU pause (vector atomics; table null = off).
-__device__ __forceinline__ int qr_cu_key() {
-  const unsigned hw = __builtin_amdgcn_s_getreg((7 << 11) | (8 << 6) | 4);   // HW_ID bits [15:8]
-  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);  // XCC_ID bits [3:0]
-  return (int)(((xcc & 7u) << 8) | (hw & 0xffu));
-}
 __device__ __forceinline__ void qr_claim(int* table) {
-  if (table && threadIdx.x == 0) __hip_atomic_fetch_add(&table[qr_cu_key()], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (table && threadIdx.x == 0) __hip_atomic_fetch_add(&table[cu_key()], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void qr_release(int* table) {
   if (!table) return;
   __syncthreads();
-  if (threadIdx.x == 0) __hip_atomic_fetch_add(&table[qr_cu_key()], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (threadIdx.x == 0) __hip_atomic_fetch_add(&table[cu_key()], -1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-int* crit_cu_table();
-int cu_yield_mode();
 
 // The TS chain's sub-panel kernels (qr_sub2c, qr_subapply: 512 threads = 2
 // waves per SIMD) are held at <= 128 VGPRs so a workgroup fits on a CU beside
@@ -54,10 +48,6 @@ int cu_yield_mode();
 #else
 #define QR_CHAIN_VGPR_CAP
 #endif
-
-void launch_gemm_batch(const GemmDesc* descs, int n, hipStream_t stream);  // tile_kernels.hip
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
 
 constexpr int kQrThreads = 256;
 constexpr int kMaxQrBatch = 32;
@@ -434,7 +424,6 @@ size_t qr_panel_workspace_bytes(const QrPanelDesc* descs, int n) {
   return b * sizeof(double);
 }
 
-void launch_qr_apply(const QrApplyDesc* descs, int n, hipStream_t stream, double* ws);
 
 // ===================================================== column-per-lane panel
 // Fast path for panels of at most 8 x kP2MaxRPT virtual rows (TSQRT with

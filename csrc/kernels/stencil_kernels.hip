@@ -13,12 +13,10 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "../device/device.hpp"
+#include "kernels.hpp"
 
 namespace parsec {
 namespace kern {
-
-using StencilArgs = StencilDesc;
 
 constexpr int kStencilKc = 16;
 constexpr int kMaxStencilBatch = 24;

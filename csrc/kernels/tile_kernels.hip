@@ -1,4 +1,10 @@
-// CDNA4 (gfx950) fp64 tile kernels for the dense linear-algebra taskpools.
+// CDNA4 (gfx950) fp64 kernels that share the per-CU claim table g_crit_cu: the
+// grouped DGEMM with its launcher, the two tile POTRFs and the W-GEMM panel
+// solve. The other families live beside it: trsm_kernels.hip (TRSM, diagonal
+// block inverses), lu_kernels.hip, inverse_kernels.hip (TRTRI / TRMM / LAUUM),
+// copy_kernels.hip; the host-only parts in gemm_plan.cpp (launch planner),
+// trsm_estimate.cpp, kernel_batch.cpp (batch dispatcher) and kernel_capi.cpp
+// (C entry points); shared device helpers in device_helpers.hpp.
 //
 //  * Grouped DGEMM / DSYRK (lower) on v_mfma_f64_16x16x4f64: ONE launch runs every
 //    ready GEMM-shaped tile task of a scheduling round, so 512^2 tiles still fill
@@ -16,10 +22,6 @@
 //    the f64 accumulator layout (col = lane&15, row = (lane>>4)+4*r, measured on
 //    MI355X: profiles/probe_mfma_f64_and_vendor_baselines.log) maps lanes to
 //    consecutive ROWS of the column-major C tile: 128-byte coalesced epilogues.
-//  * TRSM (B := B L^-T, right/lower/trans) = blocked MFMA solve with precomputed
-//    inverses of the 64x64 diagonal blocks: R_j = B_j - X_<j L_j,<j^T ; X_j = R_j invD_j^T.
-//    Each workgroup owns 16 rows and keeps its row panel in LDS with a stride of 16
-//    doubles, which makes every MFMA operand read bank-conflict free.
 //  * POTRF of a tile: per 64-column block, ONE wave factors the diagonal block
 //    (row per lane in registers, column broadcast through LDS, no block barriers)
 //    and inverts it, then the panel TRSM and the lower-only GEMM update run
@@ -30,21 +32,15 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
-#include <cstring>
-#include <mutex>
 #include <type_traits>
-#include <unordered_map>
 #include <vector>
 
-#include "../device/device.hpp"
+#include "device_helpers.hpp"
+#include "kernels.hpp"
+#include "launch_settings.hpp"
 
 namespace parsec {
 namespace kern {
-
-typedef double double4_t __attribute__((ext_vector_type(4)));
-typedef double double2_t __attribute__((ext_vector_type(2)));
-
-constexpr int kMaxGemmBatch = 40;
 
 struct GemmBatchArgs {
   int count;
@@ -63,23 +59,6 @@ struct GemmBatchArgs {
 };
 static_assert(sizeof(GemmBatchArgs) <= 4096, "GemmBatchArgs exceeds the kernel argument limit");
 
-// Issue priority of the waves of the kernels launched by this thread right now:
-// launch_kernel_batch sets it for the critical stream's batch. A critical kernel
-// sharing a CU with bulk GEMM waves otherwise gets a third of the SIMD's MFMA
-// pipe and waits behind their instructions (s_setprio: the SIMD arbitrates by
-// priority, then age).
-static thread_local int t_launch_prio = 0;
-// extra dynamic LDS of the 128x128 GEMM launched by this thread right now:
-// 8 KB pads a workgroup to 82 KB, so a CU holds ONE bulk GEMM workgroup and
-// keeps room for a critical-path tile-POTRF step workgroup (78 KB)
-static thread_local int t_launch_pad = 0;
-constexpr int kBulkPadBytes = 8192;
-#define PARSEC_WAVE_PRIO(p) do { if (p) __builtin_amdgcn_s_setprio(2); } while (0)
-// critical-path launch of this thread: its workgroups claim their CUs
-static thread_local int t_launch_claim = 0;
-// bulk launch of this thread: its GEMM waves yield claimed CUs
-static thread_local int t_launch_yield = 0;
-
 // ---- Cooperative CU yield. A critical-path workgroup (tile POTRF step, the
 // critical TRSM / SYRK GEMMs) counts itself into g_crit_cu[its CU] while it
 // runs; a bulk GEMM workgroup on the same CU polls that count once per k-tile
@@ -88,13 +67,13 @@ static thread_local int t_launch_yield = 0;
 // profiles/r4_chain16_breakdown.txt). Only the CUs that host critical work
 // pause; a pause is bounded (kYieldMaxPolls) so a stale count can never stall
 // bulk work. One counter per CU: XCC id x (CU, SH, SE) bits of HW_ID.
+// The grouped DGEMM kernel and the tile-POTRF step kernel address the table by
+// symbol, and the build has no relocatable device code: that is why they (and
+// the launchers around them) share this translation unit. Handing the table to
+// the step kernel by pointer, as the QR kernels take it (crit_cu_table), would
+// change two hot kernels.
 __device__ int g_crit_cu[8 * 256];
-__device__ __forceinline__ int cu_key() {
-  // HW_REG_HW_ID (4) bits [15:8] = CU_ID, SH_ID, SE_ID; HW_REG_XCC_ID (20) bits [3:0]
-  const unsigned hw = __builtin_amdgcn_s_getreg((7 << 11) | (8 << 6) | 4);
-  const unsigned xcc = __builtin_amdgcn_s_getreg((3 << 11) | (0 << 6) | 20);
-  return (int)(((xcc & 7u) << 8) | (hw & 0xffu));
-}
+
 __device__ __forceinline__ void crit_claim(int on) {
   if (on && threadIdx.x == 0) __hip_atomic_fetch_add(&g_crit_cu[cu_key()], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -118,27 +97,6 @@ int* crit_cu_table() {
 }
 constexpr int kYieldMaxPolls = 2000;  // x ~0.1 us sleep: at most ~0.2 ms of pause per k-tile
 __device__ __forceinline__ int crit_count(int key) { return __hip_atomic_load(&g_crit_cu[key], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-template <class Args>
-__device__ __forceinline__ int find_desc(const Args& a, const int* starts, int t) {
-  int lo = 0, hi = a.count - 1;
-  while (lo < hi) {
-    int mid = (lo + hi + 1) >> 1;
-    if (starts[mid] <= t) lo = mid;
-    else hi = mid - 1;
-  }
-  return lo;
-}
-
-// XCD-aware bijective remap: blocks b, b+8, b+16... share an XCD; give each XCD a
-// contiguous range of logical tiles.
-__device__ __forceinline__ int xcd_remap(int b, int nwg) {
-  const int nx = 8;
-  int q = nwg / nx, r = nwg % nx;
-  int x = b % nx, i = b / nx;
-  int base = x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q;
-  return base + i;
-}
 
 // ==================================================================== GEMM
 // FULL: every descriptor of the launch is a whole number of BM x BN x BK tiles
@@ -670,177 +628,10 @@ __global__ __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(WM
   gemm_tile<BM, BN, BK, WM, WN, TRANSA, TRANSB, FULL, EPI, ML>(args, tile, ks, nsplit, As, Bs);
 }
 
-// ========================================================= diag blocks (4 waves)
-// Factor the w x w (w <= 64) lower block at T (ldt) in place and/or write its
-// inverse (64 x 64 col-major, identity padded) to invD. 256 threads; lane r of
-// wave v owns row r of columns 16v..16v+15 in registers. Blocked by 16-column
-// panels so the serial chain never leaves a wave:
-//   * panel p is factored entirely inside wave p: pivots and column entries are
-//     broadcast with v_readlane (no LDS round trip, no barrier), 1/sqrt is a
-//     hardware rsq refined by two Newton steps (no IEEE divide on the chain);
-//   * the panel goes to LDS (double-buffered, one barrier per panel) and waves
-//     v > p apply the rank-16 update to their columns.
-// The inverse is blocked the same way: each wave inverts its 16x16 diagonal
-// block, then wave j walks down its block column X_ij = -X_ii sum_k L_ik X_kj.
-__device__ __forceinline__ double readlane_d(double x, int lane) {
-  const long long b = __builtin_bit_cast(long long, x);
-  const int lo = __builtin_amdgcn_readlane((int)(b & 0xffffffffll), lane);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), lane);
-  return __builtin_bit_cast(double, ((long long)hi << 32) | (unsigned int)lo);
-}
-
-__device__ __forceinline__ double rsqrt_nr(double d) {
-  double y = __builtin_amdgcn_rsq(d);
-  const double h = 0.5 * d;
-  y = y * __builtin_fma(-h * y, y, 1.5);
-  y = y * __builtin_fma(-h * y, y, 1.5);
-  return y;
-}
-
-// kUpper (inverse only, factor == false): T is upper triangular; its transpose
-// is inverted with the same code and the result is written back transposed, so
-// invD holds T^-1 (upper). T's strict lower triangle is never read.
-// kUnit (inverse only): T's diagonal is taken as 1 and never read.
-template <bool kUpper = false, bool kUnit = false>
-__device__ __forceinline__ void block_potrf64(double* T, int ldt, int w, double* invD, int* info, int info_base, bool factor) {
-  __shared__ double Ls[64][65];      // Ls[c][r] = L(r, c)
-  __shared__ double Xs[64][65];      // Xs[c][r] = X(r, c), X = L^-1
-  // The panel broadcast buffers (factor phase) and the per-wave scratch of the
-  // inverse phase share one LDS array: the kernel then fits (83 KB) next to a
-  // resident 128x128 GEMM workgroup (74 KB), so the critical-path factorization
-  // is not held back until a CU drains completely.
-  __shared__ double PnTs[2 * 16 * 65];
-  double(*Pn)[16][65] = reinterpret_cast<double(*)[16][65]>(PnTs);  // panel broadcast buffers
-  double(*Ts)[16][17] = reinterpret_cast<double(*)[16][17]>(PnTs);  // per-wave scratch for the inverse
-  __shared__ double dinv[64];
-  __shared__ int bad_s;
-  const int r = threadIdx.x & 63;
-  const int v = threadIdx.x >> 6;
-  double a[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int c = 16 * v + i;
-    if (kUpper)
-      a[i] = (r < w && c < w && !(kUnit && r == c)) ? (r >= c ? T[(size_t)r * ldt + c] : 0.0) : (r == c ? 1.0 : 0.0);
-    else
-      a[i] = (r < w && c < w && !(kUnit && r == c)) ? T[(size_t)c * ldt + r] : (r == c ? 1.0 : 0.0);
-  }
-  if (threadIdx.x == 0) bad_s = 0x7fffffff;
-  __syncthreads();
-  if (factor) {
-#pragma unroll 1
-    for (int p = 0; p < 4; ++p) {
-      double* pn = &Pn[p & 1][0][0];
-      if (v == p) {
-        int bad = 0x7fffffff;
-#pragma unroll
-        for (int jj = 0; jj < 16; ++jj) {
-          const int j = 16 * p + jj;
-          double d = readlane_d(a[jj], j);
-          if (d <= 0.0 && j < w && bad == 0x7fffffff) bad = j + 1;
-          d = d <= 0.0 ? 1.0 : d;
-          const double rs = rsqrt_nr(d);
-          const double lv = (r == j) ? d * rs : (r > j ? a[jj] * rs : 0.0);
-          a[jj] = lv;
-          if (r == j) dinv[j] = rs;
-#pragma unroll
-          for (int i = jj + 1; i < 16; ++i) a[i] -= lv * readlane_d(lv, 16 * p + i);
-        }
-        if (r == 0 && bad != 0x7fffffff) atomicMin(&bad_s, bad);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) pn[i * 65 + r] = a[i];
-      }
-      __syncthreads();
-      if (v > p) {
-        double lr[16];
-#pragma unroll
-        for (int t = 0; t < 16; ++t) lr[t] = pn[t * 65 + r];
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          double s = 0.0;
-#pragma unroll
-          for (int t = 0; t < 16; ++t) s = __builtin_fma(lr[t], pn[t * 65 + 16 * v + i], s);
-          a[i] -= s;
-        }
-      }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && bad_s != 0x7fffffff && info) atomicCAS(info, 0, info_base + bad_s);
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int c = 16 * v + i;
-      if (r < w && c < w && r >= c) T[(size_t)c * ldt + r] = a[i];
-    }
-  }
-  if (!invD) return;
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int c = 16 * v + i;
-    Ls[c][r] = (r >= c) ? a[i] : 0.0;
-    Xs[c][r] = 0.0;
-    if (!factor && r == c) dinv[c] = 1.0 / a[i];
-  }
-  __syncthreads();
-  // (1) wave v inverts its 16x16 diagonal block; lane c < 16 owns column c
-  const int b0 = 16 * v;
-  if (r < 16) {
-    double x[16];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      double s = (i == r) ? 1.0 : 0.0;
-#pragma unroll
-      for (int k = 0; k < i; ++k) s = __builtin_fma(-Ls[b0 + k][b0 + i], x[k], s);
-      x[i] = s * dinv[b0 + i];
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) Xs[b0 + r][b0 + i] = x[i];
-  }
-  __syncthreads();
-  // (2) wave j computes block column j below the diagonal, top to bottom
-  {
-    const int j = v;
-    const int c = r & 15, rg = r >> 4;  // lane -> column c, rows rg + 4q
-#pragma unroll 1
-    for (int i = j + 1; i < 4; ++i) {
-      double tq[4] = {0.0, 0.0, 0.0, 0.0};
-      for (int k = j; k < i; ++k) {
-#pragma unroll
-        for (int t = 0; t < 16; ++t) {
-          const double xv = Xs[16 * j + c][16 * k + t];
-#pragma unroll
-          for (int q = 0; q < 4; ++q) tq[q] = __builtin_fma(Ls[16 * k + t][16 * i + rg + 4 * q], xv, tq[q]);
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Ts[j][rg + 4 * q][c] = tq[q];
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0): scratch visible to the wave
-      double oq[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-      for (int t = 0; t < 16; ++t) {
-        const double tv = Ts[j][t][c];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) oq[q] = __builtin_fma(-Xs[16 * i + t][16 * i + rg + 4 * q], tv, oq[q]);
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) Xs[16 * j + c][16 * i + rg + 4 * q] = oq[q];
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_s_waitcnt(0xc07f);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int c = 16 * v + k;
-    if (kUpper)
-      invD[(size_t)r * 64 + c] = Xs[c][r];
-    else
-      invD[(size_t)c * 64 + r] = Xs[c][r];
-  }
-}
-
-constexpr int kDiagThreads = 256;
-
+// The diagonal-block kernels stay in one translation unit: the tile POTRF's
+// and the lower non-unit inverse share the LDS variables of one block_potrf64
+// instantiation, and the compiler lays these out per module -- apart, both
+// compile to different code (profiles/kernel_layer_split.txt).
 __global__ __launch_bounds__(kDiagThreads) void dpotrf_diag_inv_kernel(double* A, int lda, int j, int jb, double* invD, int* info) {
   block_potrf64(A + (size_t)j * lda + j, lda, jb, invD, info, j, true);
 }
@@ -872,527 +663,20 @@ __global__ __launch_bounds__(kDiagThreads) void dtrtri_diag_upper_unit_kernel(co
   block_potrf64<true, true>(const_cast<double*>(U) + (size_t)c0 * ldu + c0, ldu, min(64, n - c0), invD + (size_t)b * 4096, nullptr, 0, false);
 }
 
-// ==================================================================== TRSM
-constexpr int kMaxTrsmBatch = 48;
-struct TrsmInvArgs {
-  int count;
-  int prio;
-  double gate_limit;  // gated descriptors (TrsmDesc::gate) run only above this estimate
-  int block_start[kMaxTrsmBatch + 1];
-  TrsmDesc d[kMaxTrsmBatch];
-  const double* invD[kMaxTrsmBatch];
-};
-static_assert(sizeof(TrsmInvArgs) <= 4096, "TrsmInvArgs exceeds the kernel argument limit");
-
-// B := B L^-T by 64-column blocks: R_j = B_j - X_<j L_j,<j^T, X_j = R_j invD_j^T.
-// A workgroup owns BR = 16 rows of B (its row panel lives in LDS, stride 16:
-// conflict-free MFMA operand reads). 8 waves: wave (g, h) computes columns
-// 16g..16g+15 of the block over half h of the reduction, with four independent
-// MFMA accumulator chains; the two halves are summed through LDS.
-// kGlobal: the row panel stays in B itself (solved in place, 8 KB of LDS for the
-// reduction only), so the launch fits on a CU beside a resident bulk GEMM
-// workgroup: the gated fallback of the auto panel solve, whose workgroups nearly
-// always return at once (the 139 KB LDS version waited for whole CUs at
-// nb = 1024: 6.3 ms per launch on the critical stream, profiles/r4_kernel_stats_final.txt).
-// Needs n % 64 == 0. Waves of a workgroup share the CU's L1, so the in-place
-// writes of one block are visible to the next block's reads after the barrier.
-constexpr int kTrsmThreads = 512;
-template <int BR, bool kGlobal>
-__global__ __launch_bounds__(kTrsmThreads) void dtrsm_inv_kernel(const TrsmInvArgs args) {
-  static_assert(BR == 16, "MFMA operand layout assumes 16-row panels");
-  extern __shared__ double P[];  // [ncols_padded][BR], then red[16][64] (kGlobal: red only)
-  PARSEC_WAVE_PRIO(args.prio);
-  const int b = blockIdx.x;
-  const int di = find_desc(args, args.block_start, b);
-  const TrsmDesc& d = args.d[di];
-  const double* __restrict__ invD = args.invD[di];
-  // invD: contiguous 64x64 blocks, or the diagonal 64-blocks of W = L^-1 (ld invD_ld)
-  const size_t ldD = d.invD_ld ? (size_t)d.invD_ld : 64;
-  const size_t bstride = d.invD_ld ? (size_t)64 * d.invD_ld + 64 : 4096;
-  if (d.gate) {
-    const double* __restrict__ slot = d.gate_slot;
-    if (!(slot[0] * slot[1] > args.gate_limit)) return;  // the W-GEMM solved this panel
-  }
-  const bool packed = d.packed != 0;  // L(i, k) = d.L(k, i) for i > k (packed panel tile)
-  const int r0 = (b - args.block_start[di]) * BR;
-  const int n = d.n, m = d.m;
-  const int nblk = (n + 63) / 64;
-  double* red = kGlobal ? P : P + nblk * 64 * BR;
-  double* Bp = d.B;
-  const size_t ldb = d.ldb;
-  // element (row rr of the panel, column c)
-  auto pget = [&](int c, int rr) -> double {
-    if (kGlobal) return r0 + rr < m ? Bp[(size_t)c * ldb + r0 + rr] : 0.0;
-    return P[c * BR + rr];
-  };
-  auto pset = [&](int c, int rr, double v) {
-    if (kGlobal) {
-      if (r0 + rr < m) Bp[(size_t)c * ldb + r0 + rr] = v;
-    } else {
-      P[c * BR + rr] = v;
-    }
-  };
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int g = wv & 3, h = wv >> 2;
-  const int fr = lane & 15, fk = lane >> 4;
-  const double* __restrict__ L = d.L;
-  const size_t ldl = d.ldl;
-  if (!kGlobal) {
-    for (int idx = tid; idx < nblk * 64 * BR; idx += kTrsmThreads) {
-      int c = idx / BR, rr = idx % BR;
-      P[idx] = (c < n && r0 + rr < m) ? Bp[(size_t)c * ldb + r0 + rr] : 0.0;
-    }
-    __syncthreads();
-  }
-  for (int jb = 0; jb < nblk; ++jb) {
-    const int c0 = jb * 64;
-    const int cw = c0 + 16 * g + fr;  // L row this lane feeds as the MFMA A-operand
-    const bool valid = cw < n;
-    const double* __restrict__ Lp = packed ? L + (size_t)(valid ? cw : 0) * ldl : L + (valid ? cw : 0);
-    const size_t lstride = packed ? 1 : ldl;
-    double4_t acc[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] = (double4_t){0.0, 0.0, 0.0, 0.0};
-    const int kh = c0 / 2;  // multiple of 32
-    const int kbeg = h * kh, kend = kbeg + kh;
-    for (int k = kbeg; k < kend; k += 16) {
-      double av[4], bv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        av[u] = valid ? Lp[(size_t)(k + 4 * u + fk) * lstride] : 0.0;
-        bv[u] = pget(k + 4 * u + fk, fr);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc[u], 0, 0, 0);
-    }
-    double4_t s = acc[0] + acc[1] + acc[2] + acc[3];
-    if (h == 1) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) red[(g * 4 + q) * 64 + lane] = s[q];
-    }
-    __syncthreads();
-    if (h == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = c0 + 16 * g + fk + 4 * q;
-        pset(c, fr, pget(c, fr) - (s[q] + red[(g * 4 + q) * 64 + lane]));
-      }
-    }
-    __syncthreads();
-    // X_j = R_j invD_j^T, reduction over kk split between the two halves
-    double4_t t0 = (double4_t){0.0, 0.0, 0.0, 0.0}, t1 = t0;
-    const double* __restrict__ Dj = invD + (size_t)jb * bstride + 16 * g + fr;
-#pragma unroll
-    for (int kk = 32 * h; kk < 32 * h + 32; kk += 8) {
-      const double a0 = Dj[(kk + fk) * ldD], a1 = Dj[(kk + 4 + fk) * ldD];
-      const double b0 = pget(c0 + kk + fk, fr), b1 = pget(c0 + kk + 4 + fk, fr);
-      t0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, t0, 0, 0, 0);
-      t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, t1, 0, 0, 0);
-    }
-    double4_t t = t0 + t1;
-    if (h == 1) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) red[(g * 4 + q) * 64 + lane] = t[q];
-    }
-    __syncthreads();
-    if (h == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = c0 + 16 * g + fk + 4 * q;
-        pset(c, fr, t[q] + red[(g * 4 + q) * 64 + lane]);
-      }
-    }
-    __syncthreads();
-  }
-  if (!kGlobal) {
-    for (int idx = tid; idx < n * BR; idx += kTrsmThreads) {
-      int c = idx / BR, rr = idx % BR;
-      if (r0 + rr < m) Bp[(size_t)c * ldb + r0 + rr] = P[idx];
-    }
-  }
+void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream, bool unit) {
+  if (n <= 0) return;
+  if (unit)
+    hipLaunchKernelGGL(dtrtri_diag_unit_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, L, ldl, n, invD);
+  else
+    hipLaunchKernelGGL(dtrtri_diag_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, L, ldl, n, invD);
 }
 
-// ======================================================== TRSM (left side)
-constexpr int kMaxTrsmLeftBatch = 64;
-struct TrsmLeftArgs {
-  int count;
-  int prio;
-  int block_start[kMaxTrsmLeftBatch + 1];
-  TrsmLeftDesc d[kMaxTrsmLeftBatch];  // invD always set (the launcher fills it in)
-};
-static_assert(sizeof(TrsmLeftArgs) <= 4096, "TrsmLeftArgs exceeds the kernel argument limit");
-
-// B := alpha op(L)^-1 B by 64-row blocks, the scheme of dtrsm_inv_kernel turned
-// on its side. Forward (trans 0): R_j = B_j - L_j,<j X_<j, X_j = invD_j R_j;
-// backward (trans 1, j descending): R_j = B_j - L_>j,j^T X_>j, X_j = invD_j^T R_j.
-// A workgroup owns 16 columns of B for the whole sweep: the strip lives in LDS
-// as [row][16] (stride 16: conflict-free MFMA B-operand reads), its rows padded
-// with zeros to a multiple of 64, so the MFMA loops carry no masks: a lane whose
-// L row / column lies past n reads the last valid one instead (finite data times
-// the zero padding, or a result row that is written back as zero). 8 waves: wave
-// (g, h) computes rows 16g..16g+15 of the block over half h of the reduction.
-// kUpper: L is upper triangular (U). op(U) = U couples block j with the blocks
-// below it, so trans 0 is the backward sweep and trans 1 (U^T, lower) the forward
-// one; the element op(U)(i, k) sits where op(L)(i, k) does, so only the
-// direction and the side that needs the clamp differ. Either way every element
-// read lies in the named triangle.
-// TrsmLeftDesc::right: B is nrhs x n and X op(L) = alpha B, i.e. op(L)^T X^T =
-// alpha B^T: the same sweep with the transpose flipped on the strip of B^T. A
-// workgroup then owns 16 ROWS of B, LDS element [i][jj] is B[i * ldb + j0 + jj]
-// (128 contiguous bytes per column of B); only the two strip loops differ.
-// TrsmLeftDesc::unit is the launcher's business alone: the kernel reads diagonal
-// blocks only through invD.
-template <bool kUpper>
-__global__ __launch_bounds__(kTrsmThreads) void dtrsm_left_kernel(const TrsmLeftArgs args) {
-  extern __shared__ double P[];  // [rows padded][16], then red[16][64]
-  PARSEC_WAVE_PRIO(args.prio);
-  const int b = blockIdx.x;
-  const int di = find_desc(args, args.block_start, b);
-  const TrsmLeftDesc& d = args.d[di];
-  const int j0 = (b - args.block_start[di]) * 16;
-  const int n = d.n, nrhs = d.nrhs;
-  const int nblk = (n + 63) / 64;
-  const int np = nblk * 64;
-  double* red = P + np * 16;
-  const bool right = d.right != 0;
-  const bool tr = (d.trans != 0) != right;
-  const double alpha = d.alpha;
-  double* Bp = d.B;
-  const size_t ldb = d.ldb;
-  const double* __restrict__ L = d.L;
-  const size_t ldl = d.ldl;
-  const double* __restrict__ invD = d.invD;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int g = wv & 3, h = wv >> 2;
-  const int fr = lane & 15, fk = lane >> 4;
-  if (!right) {
-    for (int idx = tid; idx < np * 16; idx += kTrsmThreads) {
-      const int i = idx >> 4, jj = idx & 15;
-      P[idx] = (i < n && j0 + jj < nrhs && alpha != 0.0) ? alpha * Bp[(size_t)(j0 + jj) * ldb + i] : 0.0;
-    }
-  } else {
-    for (int idx = tid; idx < np * 16; idx += kTrsmThreads) {
-      const int i = idx >> 4, jj = idx & 15;
-      P[idx] = (i < n && j0 + jj < nrhs && alpha != 0.0) ? alpha * Bp[(size_t)i * ldb + j0 + jj] : 0.0;
-    }
-  }
-  __syncthreads();
-  const bool down = kUpper ? !tr : tr;  // backward sweep: blocks bottom up
-  for (int s = 0; s < nblk; ++s) {
-    const int jb = down ? nblk - 1 - s : s;
-    const int c0 = jb * 64;
-    const int cw = min(c0 + 16 * g + fr, n - 1);  // row (op N) / column (op T) of L this lane feeds as the MFMA A-operand
-    double4_t acc[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] = (double4_t){0.0, 0.0, 0.0, 0.0};
-    // the reduction runs over the solved blocks: above (forward) or below (backward)
-    const int kh = (down ? np - c0 - 64 : c0) / 2;  // multiple of 32
-    const int kbeg = (down ? c0 + 64 : 0) + h * kh, kend = kbeg + kh;
-    if (!tr) {
-      const double* __restrict__ Lp = L + cw;
-      for (int k = kbeg; k < kend; k += 16) {
-        double av[4], bv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int kk = k + 4 * u + fk;
-          av[u] = Lp[(size_t)(kUpper ? min(kk, n - 1) : kk) * ldl];  // upper: columns >= n meet the strip's zero padding
-          bv[u] = P[kk * 16 + fr];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc[u], 0, 0, 0);
-      }
-    } else {
-      const double* __restrict__ Lp = L + (size_t)cw * ldl;
-      for (int k = kbeg; k < kend; k += 16) {
-        double av[4], bv[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          const int kk = k + 4 * u + fk;
-          av[u] = Lp[kUpper ? kk : min(kk, n - 1)];  // lower: rows >= n meet the strip's zero padding
-          bv[u] = P[kk * 16 + fr];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc[u], 0, 0, 0);
-      }
-    }
-    double4_t sum = acc[0] + acc[1] + acc[2] + acc[3];
-    if (h == 1) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) red[(g * 4 + q) * 64 + lane] = sum[q];
-    }
-    __syncthreads();
-    if (h == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = c0 + 16 * g + fk + 4 * q;
-        P[c * 16 + fr] = c < n ? P[c * 16 + fr] - (sum[q] + red[(g * 4 + q) * 64 + lane]) : 0.0;
-      }
-    }
-    __syncthreads();
-    // X_j = op(invD_j) R_j, reduction over kk split between the two halves
-    double4_t t0 = (double4_t){0.0, 0.0, 0.0, 0.0}, t1 = t0;
-    const double* __restrict__ Dj = invD + (size_t)jb * 4096 + (tr ? (16 * g + fr) * 64 : 16 * g + fr);
-    const int dk = tr ? 1 : 64;
-#pragma unroll
-    for (int kk = 32 * h; kk < 32 * h + 32; kk += 8) {
-      const double a0 = Dj[(kk + fk) * dk], a1 = Dj[(kk + 4 + fk) * dk];
-      const double b0 = P[(c0 + kk + fk) * 16 + fr], b1 = P[(c0 + kk + 4 + fk) * 16 + fr];
-      t0 = __builtin_amdgcn_mfma_f64_16x16x4f64(a0, b0, t0, 0, 0, 0);
-      t1 = __builtin_amdgcn_mfma_f64_16x16x4f64(a1, b1, t1, 0, 0, 0);
-    }
-    double4_t t = t0 + t1;
-    if (h == 1) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) red[(g * 4 + q) * 64 + lane] = t[q];
-    }
-    __syncthreads();  // every wave has read R_j
-    if (h == 0) {
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int c = c0 + 16 * g + fk + 4 * q;
-        P[c * 16 + fr] = c < n ? t[q] + red[(g * 4 + q) * 64 + lane] : 0.0;
-      }
-    }
-    __syncthreads();
-  }
-  if (!right) {
-    for (int idx = tid; idx < n * 16; idx += kTrsmThreads) {
-      const int i = idx >> 4, jj = idx & 15;
-      if (j0 + jj < nrhs) Bp[(size_t)(j0 + jj) * ldb + i] = P[idx];
-    }
-  } else {
-    for (int idx = tid; idx < n * 16; idx += kTrsmThreads) {
-      const int i = idx >> 4, jj = idx & 15;
-      if (j0 + jj < nrhs) Bp[(size_t)i * ldb + j0 + jj] = P[idx];
-    }
-  }
-}
-
-// ================================================================ launchers
-// Every knob of the grouped-GEMM dispatch: read from the environment once
-// (gemm_policy_init, no device needed), changed afterwards by the setters below.
-struct GemmPolicy {
-  int tile = 0;          // PARSEC_GEMM_TILE: 0 auto, 64, 128
-  int full = 1;          // PARSEC_GEMM_FULL=0 disables the unchecked fast path
-  int big_tiles = 384;   // PARSEC_GEMM_BIG_TILES: 128x128 tiles in a launch to pick the big kernel
-  int splitk = 1;        // PARSEC_GEMM_SPLITK=0 disables the split-K tail of the 128x128 kernel (tests/test_headline_gpu.py, profiles/r2_bench_ab_fill_splitk.log)
-  int mainloop = 1;      // PARSEC_GEMM_MAINLOOP: k loop of the full launches, 0 plain, 1 rotated (profiles/gemm_rotated_mainloop.txt, tests/test_gemm_mainloop_gpu.py)
-  int pipeline = 1;      // PARSEC_GEMM_PIPELINE: body of the rotated k loop, 0 compiler-scheduled, 1 pinned (gemm_tile ML = 2; profiles/gemm_pipelined_mainloop.txt, tests/test_gemm_pipeline_gpu.py)
-  int chunk_fill = 1;    // PARSEC_GEMM_CHUNK_FILL=0: fixed 40-descriptor launches
-  int slots = 0;         // PARSEC_GEMM_SLOTS: resident 128x128 workgroups, one round of the big kernel; 0 = two per CU of the device
-  // PARSEC_GEMM_EPI: the atomic epilogue 1 always, 0 never, -1 when every
-  // descriptor has K >= 1024: 40 x 1024^3 61.6 -> 63.9 TF, 16 x 1024^3 57.9 ->
-  // 58.9 TF, but 32 x 512^3 51.3 -> 47.5 TF (half the flops per memory-side
-  // add) -- profiles/r5_gemm_epilogue.txt
-  int epi = -1;
-  bool pad_test = false;   // PARSEC_GEMM_PAD_TEST=1: parsec_amd_dgemm_batch launches like a DPOTRF bulk stream
-  bool pad_debug = false;  // PARSEC_GEMM_PAD_DEBUG: say so once when a padded launch goes out
-};
-static GemmPolicy gemm_policy_init() {
-  GemmPolicy p;
-  auto num = [](const char* name, int& v) {
-    if (const char* e = getenv(name)) v = atoi(e);
-  };
-  num("PARSEC_GEMM_TILE", p.tile);
-  num("PARSEC_GEMM_FULL", p.full);
-  num("PARSEC_GEMM_BIG_TILES", p.big_tiles);
-  num("PARSEC_GEMM_SPLITK", p.splitk);
-  num("PARSEC_GEMM_MAINLOOP", p.mainloop);
-  num("PARSEC_GEMM_PIPELINE", p.pipeline);
-  num("PARSEC_GEMM_CHUNK_FILL", p.chunk_fill);
-  num("PARSEC_GEMM_SLOTS", p.slots);
-  num("PARSEC_GEMM_EPI", p.epi);
-  p.mainloop = p.mainloop != 0;
-  p.pipeline = p.pipeline != 0;
-  if (getenv("PARSEC_GEMM_SLOTS")) p.slots = std::max(1, p.slots);
-  if (p.epi != 0 && p.epi != 1) p.epi = -1;
-  int pad_test = 0;
-  num("PARSEC_GEMM_PAD_TEST", pad_test);
-  p.pad_test = pad_test != 0;
-  p.pad_debug = getenv("PARSEC_GEMM_PAD_DEBUG") != nullptr;
-  return p;
-}
-static GemmPolicy& gemm_policy() {
-  static GemmPolicy p = gemm_policy_init();
-  return p;
-}
-// resident 128x128 workgroups of the launch being issued: half when bulk
-// launches are padded to one workgroup per CU (t_launch_pad)
-static int gemm_slots() {
-  static const int device_slots = [] {
-    int dev = 0, ncu = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) return 2 * ncu;
-    return 512;
-  }();
-  const int slots = gemm_policy().slots > 0 ? gemm_policy().slots : device_slots;
-  return t_launch_pad ? std::max(1, slots / 2) : slots;
-}
-
-// The pinned body addresses an operand as a uniform base plus a 32-bit
-// per-thread byte offset that spans the columns of the stored operand a k-tile
-// touches: BK of A (BM when A is transposed), BN of B (BK when B is transposed).
-int gemm_pipeline_fits(int bm, int bn, int bk, int transA, int transB, long long lda, long long ldb) {
-  const unsigned long long span_a = (unsigned long long)(transA ? bm : bk) * (unsigned long long)lda * sizeof(double);
-  const unsigned long long span_b = (unsigned long long)(transB ? bk : bn) * (unsigned long long)ldb * sizeof(double);
-  // strictly below 2^32: the buffer resource of the loads covers 2^32 - 1 bytes
-  return span_a < (1ull << 32) && span_b < (1ull << 32);
-}
-
-// launch record of this thread (gemm_launch_log): a ring of the last launches
-static thread_local bool t_gemm_log_on = false;
-static thread_local GemmLaunchRecord t_gemm_log[kGemmLaunchLogSize];
-static thread_local unsigned t_gemm_log_count = 0;  // records written since the last reset
-
-// ---- Decide. What launch_gemm_batch issues for a descriptor list is computed
-// here on the host alone, from the descriptors and an explicit environment; no
-// pointer is dereferenced and no device is asked.
-struct GemmPlanEnv {
-  GemmPolicy policy;
-  int slots;      // resident 128x128 workgroups of one round (already halved for a padded launch)
-  int pad_bytes;  // extra dynamic LDS of a 128x128 launch (one bulk workgroup per CU)
-  bool yield;     // bulk launch: the waves poll their CU's claim count
-  bool claim;     // critical launch: the workgroups claim their CUs
-};
-// one launch: its record and its descriptors, [first, first + rec.descs) of the regrouped list
-struct GemmLaunch {
-  GemmLaunchRecord rec;
-  int first;
-};
-
-// Descriptors per launch (<= kMaxGemmBatch, the kernel-argument limit): the cut
-// that fills whole rounds of resident 128x128 workgroups best. 40 tiles of
-// 512^2 are 640 128-tiles = 1.25 rounds of 512 slots (62 % of the second round
-// idle); 32 of them are exactly one round.
-template <class Tiles128>  // tiles128(i): 128 x 128 tiles of descriptor i
-static int gemm_chunk_cut(Tiles128 tiles128, int n, int slots, bool fill_rounds) {
-  const int cap = std::min(n, kMaxGemmBatch);
-  if (!fill_rounds) return cap;
-  int best = cap, tiles = 0;
-  double best_fill = -1.0;
-  for (int c = 1; c <= cap; ++c) {
-    tiles += tiles128(c - 1);
-    if (tiles < slots) continue;
-    const int rounds = (tiles + slots - 1) / slots;
-    const double fill = (double)tiles / ((double)rounds * slots);
-    if (fill >= best_fill - 1e-9) { best_fill = fill; best = c; }  // ties: the larger cut
-  }
-  return best_fill >= 0.0 ? best : cap;
-}
-int gemm_chunk_plan(const int* m, const int* n, int count, int slots, int* out) {
-  int cuts = 0;
-  for (int s = 0; s < count;) {
-    const int c = gemm_chunk_cut([&](int i) { return ((m[s + i] + 127) / 128) * ((n[s + i] + 127) / 128); }, count - s, std::max(1, slots),
-                                 gemm_policy().chunk_fill != 0);
-    out[cuts++] = c;
-    s += c;
-  }
-  return cuts;
-}
-
-// One launch of n descriptors of one operand mode: tile shape, kernel, grid.
-static GemmLaunchRecord gemm_plan_launch(const GemmDesc* descs, int n, const GemmPlanEnv& env) {
-  const GemmPolicy& p = env.policy;
-  GemmLaunchRecord r{};
-  int t128 = 0;
-  bool big = true;
-  for (int i = 0; i < n; ++i) {
-    t128 += ((descs[i].m + 127) / 128) * ((descs[i].n + 127) / 128);
-    if (descs[i].m < 128 || descs[i].n < 128) big = false;
-  }
-  // 128x128: 8 waves (2 x 4) of 64x32, 126 VGPRs -> 4 waves per SIMD with two
-  // workgroups per CU (profiles/r1_gemm_variants_v8.log); 64x64: 4 waves of 32x32
-  const bool use_big = p.tile == 128 || (p.tile == 0 && big && t128 >= p.big_tiles);
-  const int BM = use_big ? 128 : 64, BN = BM, BK = 16;
-  r.bm = BM; r.bn = BN;
-  r.descs = n;
-  r.transA = descs[0].transA != 0; r.transB = descs[0].transB != 0;
-  r.pad_bytes = use_big ? env.pad_bytes : 0;
-  int total = 0;
-  bool full = p.full != 0;
-  for (int i = 0; i < n; ++i) {
-    const GemmDesc& g = descs[i];
-    full = full && g.m % BM == 0 && g.n % BN == 0 && g.k > 0 && g.k % BK == 0 && (g.lda | g.ldb) % 2 == 0 &&
-           ((uintptr_t)g.A | (uintptr_t)g.B) % 16 == 0;
-    total += ((g.m + BM - 1) / BM) * ((g.n + BN - 1) / BN);
-  }
-  r.total_tiles = r.main_tiles = r.grid = total;
-  r.ksplit = 1;
-  const int slots = env.slots;
-  if (use_big && p.splitk != 0 && total > slots) {
-    // the last partial round of workgroups: split its tiles' K range so it
-    // finishes in 1/s of a tile time; needs beta == 1 (partials are added into C)
-    // and >= 256 of K per chunk (fewer flops per added byte would be bound by
-    // the chip's f64 atomic rate)
-    const int tail = total % slots;
-    int kmin = 1 << 30;
-    bool ok = tail > 0 && 2 * tail <= slots;
-    for (int i = 0; ok && i < n; ++i) {
-      ok = descs[i].beta == 1.0 && !descs[i].a_lower && !descs[i].b_upper && !descs[i].Cin && !descs[i].C2;
-      kmin = std::min(kmin, descs[i].k);
-    }
-    const int s = ok ? std::min({slots / std::max(tail, 1), kmin / 256, 8}) : 1;
-    if (s >= 2) {
-      r.main_tiles = total - tail;
-      r.ksplit = s;
-      r.grid = r.main_tiles + tail * s;
-    }
-  }
-  // atomic epilogue: every descriptor accumulates into C (beta 1, no separate Cin / C2)
-  bool epi = p.epi != 0 && full;
-  for (int i = 0; epi && i < n; ++i) epi = descs[i].beta == 1.0 && !descs[i].Cin && !descs[i].C2 && (p.epi > 0 || descs[i].k >= 1024);
-  // rotated k loop (gemm_tile ML = 1) for the full launches
-  const bool rot = full && p.mainloop == 1;
-  // its pinned body (ML = 2): no yield poll or CU claim, 32-bit per-thread operand offsets
-  bool pipe = rot && p.pipeline == 1 && !env.yield && !env.claim;
-  for (int i = 0; pipe && i < n; ++i) pipe = gemm_pipeline_fits(BM, BN, BK, descs[i].transA, descs[i].transB, descs[i].lda, descs[i].ldb) != 0;
-  r.full = full; r.epilogue = epi ? 1 : 0;
-  r.rotated = rot; r.pipelined = pipe;
-  return r;
-}
-
-// Group descriptors by (transA, transB): one grouped launch per combination
-// (the vendor library is an A/B reference only: scripts/kbench_gemm_vs_vendor.py).
-// A descriptor with alpha == 0 or k <= 0 references neither A nor B (BLAS): it
-// goes out as K = 0 in a launch of its own kind, C := beta C from the
-// bounds-checked kernel's epilogue, so NaN / Inf in the operands stay out of C
-// and the k loops carry no test for it. (Gated descriptors are a protocol of
-// the panel solve and stay where they are.) `sorted` receives the descriptors
-// in launch order; a chunk without tiles launches nothing and has no record.
-static std::vector<GemmLaunch> gemm_plan(const GemmDesc* descs, int n, const GemmPlanEnv& env, std::vector<GemmDesc>& sorted) {
-  std::vector<GemmDesc> g[5];
-  for (int i = 0; i < n; ++i) {
-    const GemmDesc& d = descs[i];
-    if ((d.alpha == 0.0 || d.k <= 0) && !d.gate) {
-      GemmDesc z = d;
-      z.k = 0;
-      z.transA = z.transB = 0;
-      z.a_lower = z.b_upper = 0;
-      g[4].push_back(z);
-    } else {
-      g[(d.transA ? 2 : 0) | (d.transB ? 1 : 0)].push_back(d);
-    }
-  }
-  std::vector<GemmLaunch> plan;
-  sorted.clear();
-  for (const auto& v : g) {
-    for (size_t s = 0; s < v.size();) {
-      const GemmDesc* d = v.data() + s;
-      const int c = gemm_chunk_cut([d](int i) { return ((d[i].m + 127) / 128) * ((d[i].n + 127) / 128); }, (int)(v.size() - s), env.slots,
-                                   env.policy.chunk_fill != 0);
-      const GemmLaunchRecord r = gemm_plan_launch(d, c, env);
-      if (r.total_tiles > 0) plan.push_back({r, (int)sorted.size()});
-      sorted.insert(sorted.end(), d, d + c);
-      s += (size_t)c;
-    }
-  }
-  return plan;
-}
-int gemm_launch_plan(const GemmDesc* descs, int n, int slots, bool one_per_cu, bool bulk_yield, int claim, GemmLaunchRecord* out) {
-  std::vector<GemmDesc> sorted;
-  const GemmPlanEnv env{gemm_policy(), std::max(1, one_per_cu ? slots / 2 : slots), one_per_cu ? kBulkPadBytes : 0, bulk_yield, claim >= 2};
-  const std::vector<GemmLaunch> plan = gemm_plan(descs, n, env, sorted);
-  for (size_t i = 0; i < plan.size(); ++i) out[i] = plan[i].rec;
-  return (int)plan.size();
+void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipStream_t stream, bool unit) {
+  if (n <= 0) return;
+  if (unit)
+    hipLaunchKernelGGL(dtrtri_diag_upper_unit_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, U, ldu, n, invD);
+  else
+    hipLaunchKernelGGL(dtrtri_diag_upper_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, U, ldu, n, invD);
 }
 
 // ---- Launch.
@@ -1423,16 +707,29 @@ static void launch_gemm_shape(const GemmLaunchRecord& r, const GemmBatchArgs& a,
   }
 }
 
+// resident 128x128 workgroups of the launch being issued: half when bulk
+// launches are padded to one workgroup per CU (LaunchSettings::pad)
+static int gemm_slots() {
+  static const int device_slots = [] {
+    int dev = 0, ncu = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && ncu > 0) return 2 * ncu;
+    return 512;
+  }();
+  const int slots = gemm_policy().slots > 0 ? gemm_policy().slots : device_slots;
+  return launch_settings().pad ? std::max(1, slots / 2) : slots;
+}
+
 // Issues the plan: every launch is driven by its record, and the record is
 // what the launch log keeps.
 void launch_gemm_batch(const GemmDesc* descs, int n, hipStream_t stream) {
-  const GemmPlanEnv env{gemm_policy(), gemm_slots(), t_launch_pad, t_launch_yield != 0, t_launch_claim >= 2};
+  const LaunchSettings& ls = launch_settings();
+  const GemmPlanEnv env{gemm_policy(), gemm_slots(), ls.pad, ls.yield != 0, ls.claim >= 2};
   std::vector<GemmDesc> sorted;
   for (const GemmLaunch& l : gemm_plan(descs, n, env, sorted)) {
     const GemmLaunchRecord& r = l.rec;
     GemmBatchArgs a;
     a.count = r.descs;
-    a.prio = t_launch_prio;
+    a.prio = ls.prio;
     a.claim = env.claim;
     a.yield = env.yield;
     a.total_tiles = r.total_tiles;
@@ -1454,416 +751,9 @@ void launch_gemm_batch(const GemmDesc* descs, int n, hipStream_t stream) {
         std::fprintf(stderr, "[gemm] bulk 128x128 launch with %d extra LDS bytes (one workgroup per CU)\n", r.pad_bytes);
       }
     }
-    if (t_gemm_log_on) t_gemm_log[t_gemm_log_count++ % kGemmLaunchLogSize] = r;
+    gemm_launch_log_append(r);
     if (r.bm == 128) launch_gemm_shape<128, 128, 16, 2, 4>(r, a, stream);
     else launch_gemm_shape<64, 64, 16, 2, 2>(r, a, stream);
-  }
-}
-
-// Split-K tail of the 128x128 kernel on (1) / off (0), < 0 queries; returns the previous setting.
-int gemm_splitk(int on) {
-  const int prev = gemm_policy().splitk;
-  if (on >= 0) gemm_policy().splitk = on;
-  return prev;
-}
-
-// k loop of the full register-staged GEMM launches: 0 plain, 1 rotated, < 0 queries; returns the previous setting.
-int gemm_mainloop(int mode) {
-  const int prev = gemm_policy().mainloop;
-  if (mode >= 0) gemm_policy().mainloop = mode == 0 ? 0 : 1;
-  return prev;
-}
-
-// Body of the rotated k loop (consulted only when gemm_mainloop is 1): 0 compiler-scheduled, 1 pinned, < 0 queries; returns the previous setting.
-int gemm_pipeline(int mode) {
-  const int prev = gemm_policy().pipeline;
-  if (mode >= 0) gemm_policy().pipeline = mode == 0 ? 0 : 1;
-  return prev;
-}
-
-// Round-filling launch chunks on (1) / off (0), < 0 queries; returns the previous setting.
-int gemm_chunk_fill(int on) {
-  const int prev = gemm_policy().chunk_fill;
-  if (on >= 0) gemm_policy().chunk_fill = on != 0;
-  return prev;
-}
-
-int gemm_launch_log(int on) {
-  const int prev = t_gemm_log_on;
-  if (on >= 0) t_gemm_log_on = on != 0;
-  return prev;
-}
-
-int gemm_launch_log_read(GemmLaunchRecord* out, bool reset) {
-  const unsigned have = std::min<unsigned>(t_gemm_log_count, kGemmLaunchLogSize);
-  for (unsigned i = 0; i < have; ++i) out[i] = t_gemm_log[(t_gemm_log_count - have + i) % kGemmLaunchLogSize];
-  if (reset) t_gemm_log_count = 0;
-  return (int)have;
-}
-
-// Tile-size policy of the grouped GEMM (0 = auto, 64, 128); returns the previous one.
-int gemm_tile_policy(int p) {
-  const int prev = gemm_policy().tile;
-  if (p >= 0) gemm_policy().tile = p;
-  return prev;
-}
-
-static constexpr int kTrsmRows = 16;
-static constexpr int kTrsmMaxCols = 18 * 64;  // LDS bound: (18*64*16 + 1024) doubles < 160 KiB
-
-// invD[i] must already hold the inverted diagonal blocks of descs[i].L.
-// in_place: the small-LDS variant (every n a multiple of 64; see dtrsm_inv_kernel)
-void launch_trsm_inv(const TrsmDesc* descs, const double* const* invD, int n, hipStream_t stream, bool in_place = false) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)dtrsm_inv_kernel<kTrsmRows, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  for (int s0 = 0; s0 < n; s0 += kMaxTrsmBatch) {
-    int cnt = std::min(kMaxTrsmBatch, n - s0);
-    TrsmInvArgs a;
-    a.count = cnt;
-    a.prio = t_launch_prio;
-    a.gate_limit = parsec::trsm_inverse_limit();
-    int total = 0, maxn = 0;
-    for (int i = 0; i < cnt; ++i) {
-      a.d[i] = descs[s0 + i];
-      a.invD[i] = invD[s0 + i];
-      a.block_start[i] = total;
-      total += (a.d[i].m + kTrsmRows - 1) / kTrsmRows;
-      maxn = std::max(maxn, a.d[i].n);
-      if (in_place && a.d[i].n % 64 != 0) fatal("dtrsm in-place kernel: n=%d is not a multiple of 64", a.d[i].n);
-    }
-    a.block_start[cnt] = total;
-    if (total == 0) continue;
-    if (in_place) {
-      hipLaunchKernelGGL((dtrsm_inv_kernel<kTrsmRows, true>), dim3(total), dim3(kTrsmThreads), 1024 * sizeof(double), stream, a);
-      continue;
-    }
-    if (maxn > kTrsmMaxCols) fatal("dtrsm tile kernel: n=%d exceeds the LDS-resident panel limit %d", maxn, kTrsmMaxCols);
-    size_t lds = ((size_t)((maxn + 63) / 64) * 64 * kTrsmRows + 1024) * sizeof(double);
-    hipLaunchKernelGGL((dtrsm_inv_kernel<kTrsmRows, false>), dim3(total), dim3(kTrsmThreads), lds, stream, a);
-  }
-}
-
-size_t trsm_workspace_bytes(const TrsmDesc* descs, int n) {
-  size_t bytes = 0;
-  std::vector<const double*> seen;
-  for (int i = 0; i < n; ++i) {
-    if (descs[i].invD) continue;
-    if (std::find(seen.begin(), seen.end(), descs[i].L) != seen.end()) continue;
-    seen.push_back(descs[i].L);
-    bytes += (size_t)((descs[i].n + 63) / 64) * 4096 * sizeof(double);
-  }
-  return bytes;
-}
-
-// Diagonal-block inverses come from the descriptor (kept by POTRF) or are
-// computed once per distinct L into the workspace.
-void launch_trsm_batch(const TrsmDesc* descs, int n, hipStream_t stream, double* ws) {
-  if (n <= 0) return;
-  std::vector<std::pair<const double*, const double*>> seen;  // L -> inverse blocks
-  std::vector<const double*> inv(n);
-  size_t off = 0;
-  for (int i = 0; i < n; ++i) {
-    if (descs[i].invD) { inv[i] = descs[i].invD; continue; }
-    auto it = std::find_if(seen.begin(), seen.end(), [&](const auto& e) { return e.first == descs[i].L; });
-    if (it != seen.end()) { inv[i] = it->second; continue; }
-    int nblk = (descs[i].n + 63) / 64;
-    double* blk = ws + off;
-    off += (size_t)nblk * 4096;
-    hipLaunchKernelGGL(dtrtri_diag_kernel, dim3(nblk), dim3(kDiagThreads), 0, stream, descs[i].L, descs[i].ldl, descs[i].n, blk);
-    seen.emplace_back(descs[i].L, blk);
-    inv[i] = blk;
-  }
-  launch_trsm_inv(descs, inv.data(), n, stream);
-}
-
-void launch_trtri_diag(const double* L, int ldl, int n, double* invD, hipStream_t stream, bool unit) {
-  if (n <= 0) return;
-  if (unit)
-    hipLaunchKernelGGL(dtrtri_diag_unit_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, L, ldl, n, invD);
-  else
-    hipLaunchKernelGGL(dtrtri_diag_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, L, ldl, n, invD);
-}
-
-void launch_trtri_diag_upper(const double* U, int ldu, int n, double* invD, hipStream_t stream, bool unit) {
-  if (n <= 0) return;
-  if (unit)
-    hipLaunchKernelGGL(dtrtri_diag_upper_unit_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, U, ldu, n, invD);
-  else
-    hipLaunchKernelGGL(dtrtri_diag_upper_kernel, dim3((n + 63) / 64), dim3(kDiagThreads), 0, stream, U, ldu, n, invD);
-}
-
-// a matrix and the triangle of it that is solved with: the lower and the upper
-// triangle of one pointer are different matrices, and so are the unit and the
-// non-unit reading of one triangle (bit 0: upper, bit 1: unit). The side is not
-// part of it: a right-side solve uses the same inverses.
-using TrsmLeftKey = std::pair<const double*, int>;
-static inline TrsmLeftKey trsm_left_key(const TrsmLeftDesc& d) { return {d.L, (d.upper ? 1 : 0) | (d.unit ? 2 : 0)}; }
-
-size_t trsm_left_workspace_bytes(const TrsmLeftDesc* descs, int n) {
-  size_t bytes = 0;
-  std::vector<TrsmLeftKey> seen;
-  for (int i = 0; i < n; ++i) {
-    if (descs[i].invD || descs[i].n <= 0) continue;
-    const TrsmLeftKey key = trsm_left_key(descs[i]);
-    if (std::find(seen.begin(), seen.end(), key) != seen.end()) continue;
-    seen.push_back(key);
-    bytes += (size_t)((descs[i].n + 63) / 64) * 4096 * sizeof(double);
-  }
-  return bytes;
-}
-
-// Left-side solves, one workgroup per 16 columns of every B. Diagonal-block
-// inverses come from the descriptor or are computed once per distinct (L,
-// triangle, unit) into ws. The lower and the upper descriptors go to their own
-// instantiation of the kernel, each grouped 64 at a time in submission order.
-void launch_trsm_left_batch(const TrsmLeftDesc* descs, int n, hipStream_t stream, double* ws) {
-  if (n <= 0) return;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)dtrsm_left_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute((const void*)dtrsm_left_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  std::vector<std::pair<TrsmLeftKey, const double*>> seen;  // (L, triangle) -> inverse blocks
-  std::vector<const double*> inv(n, nullptr);
-  std::vector<int> order[2];  // descriptor indices per triangle
-  size_t off = 0;
-  for (int i = 0; i < n; ++i) {
-    const bool up = descs[i].upper != 0;
-    order[up].push_back(i);
-    if (descs[i].n <= 0 || descs[i].nrhs <= 0) continue;
-    if (descs[i].invD) { inv[i] = descs[i].invD; continue; }
-    const TrsmLeftKey key = trsm_left_key(descs[i]);
-    auto it = std::find_if(seen.begin(), seen.end(), [&](const auto& e) { return e.first == key; });
-    if (it != seen.end()) { inv[i] = it->second; continue; }
-    int nblk = (descs[i].n + 63) / 64;
-    double* blk = ws + off;
-    off += (size_t)nblk * 4096;
-    if (up)
-      launch_trtri_diag_upper(descs[i].L, descs[i].ldl, descs[i].n, blk, stream, descs[i].unit != 0);
-    else
-      launch_trtri_diag(descs[i].L, descs[i].ldl, descs[i].n, blk, stream, descs[i].unit != 0);
-    seen.emplace_back(key, blk);
-    inv[i] = blk;
-  }
-  for (int up = 0; up < 2; ++up) {
-    const std::vector<int>& idx = order[up];
-    const int nd = (int)idx.size();
-    for (int s0 = 0; s0 < nd; s0 += kMaxTrsmLeftBatch) {
-      const int cnt = std::min(kMaxTrsmLeftBatch, nd - s0);
-      TrsmLeftArgs a;
-      a.count = cnt;
-      a.prio = t_launch_prio;
-      int total = 0, maxn = 0;
-      for (int i = 0; i < cnt; ++i) {
-        a.d[i] = descs[idx[s0 + i]];
-        a.d[i].invD = inv[idx[s0 + i]];
-        a.block_start[i] = total;
-        if (a.d[i].n <= 0 || a.d[i].nrhs <= 0) continue;
-        total += (a.d[i].nrhs + 15) / 16;
-        maxn = std::max(maxn, a.d[i].n);
-      }
-      a.block_start[cnt] = total;
-      if (total == 0) continue;
-      if (maxn > kTrsmMaxCols) fatal("dtrsm left tile kernel: n=%d exceeds the LDS-resident strip limit %d", maxn, kTrsmMaxCols);
-      const size_t lds = ((size_t)((maxn + 63) / 64) * 64 * 16 + 1024) * sizeof(double);
-      if (up)
-        hipLaunchKernelGGL(dtrsm_left_kernel<true>, dim3(total), dim3(kTrsmThreads), lds, stream, a);
-      else
-        hipLaunchKernelGGL(dtrsm_left_kernel<false>, dim3(total), dim3(kTrsmThreads), lds, stream, a);
-    }
-  }
-}
-
-// ================================== tile GETRF without pivoting (A = L U)
-// Right-looking, blocked by 64 columns, three launches per block column j:
-//   dgetrf_diag_kernel   one workgroup: A_jj := L_jj \ U_jj in registers, then
-//                        inv(L_jj) (unit lower) and inv(U_jj) the same way
-//   dgetrf_panel_kernel  one workgroup per 64 x 64 block of the block column
-//                        below (A_ij := A_ij inv(U_jj)) and of the block row to
-//                        the right (A_jk := inv(L_jj) A_jk): one 64^3 product on
-//                        v_mfma_f64_16x16x4f64 from LDS
-//   the grouped NN GEMM  A_ik -= A_ij A_jk over the trailing part
-// No pivoting: a zero pivot is reported and the factorization goes on with
-// inf / nan. 50 KB (diagonal) and 75 KB (panel) of LDS: either fits beside one
-// resident 128 x 128 GEMM workgroup.
-constexpr int kGetrfLd = 65;   // F of the diagonal kernel: [column][row], one pad
-constexpr int kGetrfLdA = 80;  // MFMA A operand [k][row]: the two k of a 32-lane half land 32 banks apart
-constexpr int kGetrfLdB = 66;  // MFMA B operand [column][k]: 16 columns x 2 k on 32 distinct bank pairs
-
-__global__ __launch_bounds__(256) void dgetrf_diag_kernel(double* A, int lda, int j, int w, double* invL, double* invU, int* info, int info_base, int prio) {
-  __shared__ double F[64 * kGetrfLd];      // F[c][r] = (L\U)(r, c), identity-padded past w
-  __shared__ double Pn[2 * 16 * kGetrfLd];  // the two panel broadcast buffers
-  __shared__ double rcp[64];  // 1 / U(c, c)
-  __shared__ int bad_s;
-  PARSEC_WAVE_PRIO(prio);
-  double* T = A + (size_t)j * lda + j;
-  const int r = threadIdx.x & 63;
-  const int v = threadIdx.x >> 6;
-  // thread (r, v): row r, columns 16v .. 16v+15
-  double a[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int c = 16 * v + i;
-    a[i] = (r < w && c < w) ? T[(size_t)c * lda + r] : (r == c ? 1.0 : 0.0);
-  }
-  if (threadIdx.x == 0) bad_s = 0x7fffffff;
-  __syncthreads();
-#pragma unroll 1
-  for (int p = 0; p < 4; ++p) {
-    double* pn = Pn + (p & 1) * 16 * kGetrfLd;
-    if (v == p) {
-      // wave p factors its 64 x 16 panel: lane jc holds row jc of U
-      int bad = 0x7fffffff;
-#pragma unroll
-      for (int jj = 0; jj < 16; ++jj) {
-        const int jc = 16 * p + jj;
-        const double d = readlane_d(a[jj], jc);
-        if (d == 0.0 && bad == 0x7fffffff) bad = jc + 1;  // the padding's pivots are 1
-        const double rd = 1.0 / d;
-        if (r > jc) a[jj] *= rd;
-        const double lv = r > jc ? a[jj] : 0.0;
-#pragma unroll
-        for (int i = jj + 1; i < 16; ++i) a[i] = __builtin_fma(-lv, readlane_d(a[i], jc), a[i]);
-        if (r == jc) rcp[jc] = rd;
-      }
-      if (r == 0 && bad != 0x7fffffff) atomicMin(&bad_s, bad);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) pn[i * kGetrfLd + r] = a[i];
-    }
-    __syncthreads();
-    if (v > p) {
-      // the columns to the right: row 16p+s of U is final once the rows above it
-      // were applied; every row below takes its multiple (solve and update in one)
-#pragma unroll
-      for (int s = 0; s < 16; ++s) {
-        const int js = 16 * p + s;
-        const double l = r > js ? pn[s * kGetrfLd + r] : 0.0;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) a[i] = __builtin_fma(-l, readlane_d(a[i], js), a[i]);
-      }
-    }
-  }
-  if (threadIdx.x == 0 && bad_s != 0x7fffffff && info) {
-    const int val = info_base + j + bad_s;
-    const int old = atomicCAS(info, 0, val);
-    if (old != 0 && val < old) atomicMin(info, val);
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int c = 16 * v + i;
-    if (r < w && c < w) T[(size_t)c * lda + r] = a[i];
-    F[c * kGetrfLd + r] = a[i];
-  }
-  __syncthreads();
-  // The inverses by the same elimination on the identity, again with a row per
-  // lane and 16 columns per wave: X = inv(L) from L X = I, and Y = inv(U)^T from
-  // U^T Y = I (U^T is lower, with U's diagonal). Row js of either is final when
-  // step js starts; the rows below take their multiple of it. Columns 16v.. of a
-  // row js < 16v are still zero, so wave v starts at js = 16v.
-  double x[16], y[16];
-#pragma unroll
-  for (int i = 0; i < 16; ++i) x[i] = y[i] = (r == 16 * v + i) ? 1.0 : 0.0;
-#pragma unroll 1
-  for (int js = 16 * v; js < 64; ++js) {
-    const double l = r > js ? F[js * kGetrfLd + r] : 0.0;  // L(r, js)
-    const double u = r > js ? F[r * kGetrfLd + js] : 0.0;  // U(js, r) = U^T(r, js)
-    const double rd = rcp[js];
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      x[i] = __builtin_fma(-l, readlane_d(x[i], js), x[i]);
-      const double yj = readlane_d(y[i], js) * rd;
-      y[i] = r == js ? yj : __builtin_fma(-u, yj, y[i]);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < 16; ++i) {
-    const int c = 16 * v + i;
-    if (invL) invL[(size_t)c * 64 + r] = x[i];  // inv(L)(r, c)
-    if (invU) invU[(size_t)r * 64 + c] = y[i];  // inv(U)(c, r) = Y(r, c)
-  }
-}
-
-// blockIdx.x < nrb: block i of the column panel, A_ij := A_ij inv(U_jj);
-// else block k of the row panel, A_jk := inv(L_jj) A_jk. The diagonal block is a
-// full 64 x 64 one (there is no panel after a ragged one).
-__global__ __launch_bounds__(256) void dgetrf_panel_kernel(double* A, int lda, int n, int j, const double* __restrict__ invL, const double* __restrict__ invU, int nrb, int prio) {
-  __shared__ double As[64 * kGetrfLdA];  // As[k][row]: the left factor of the product
-  __shared__ double Bs[64 * kGetrfLdB];  // Bs[column][k]: the right factor
-  PARSEC_WAVE_PRIO(prio);
-  const bool below = (int)blockIdx.x < nrb;
-  const int o = j + 64 + 64 * (below ? (int)blockIdx.x : (int)blockIdx.x - nrb);
-  const int wb = min(64, n - o);
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int fr = lane & 15, fk = lane >> 4;
-  // the block of A: rows r0.., columns c0.., mr x nc valid
-  const int r0 = below ? o : j, c0 = below ? j : o;
-  const int mr = below ? wb : 64, nc = below ? 64 : wb;
-  double* __restrict__ Ab = A + (size_t)c0 * lda + r0;
-  for (int idx = tid; idx < 4096; idx += 256) {
-    const int lo = idx & 63, hi = idx >> 6;
-    if (below) {
-      As[hi * kGetrfLdA + lo] = lo < mr ? Ab[(size_t)hi * lda + lo] : 0.0;  // A_ij(row lo, k hi)
-      Bs[hi * kGetrfLdB + lo] = invU[hi * 64 + lo];                         // inv(U)(k lo, column hi)
-    } else {
-      As[hi * kGetrfLdA + lo] = invL[hi * 64 + lo];                         // inv(L)(row lo, k hi)
-      Bs[hi * kGetrfLdB + lo] = hi < nc ? Ab[(size_t)hi * lda + lo] : 0.0;  // A_jk(k lo, column hi)
-    }
-  }
-  __syncthreads();
-  // wave wv: rows 16wv .. 16wv+15 of the product, four 16-column accumulators
-  double4_t acc[4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u) acc[u] = (double4_t){0.0, 0.0, 0.0, 0.0};
-#pragma unroll 4
-  for (int kk = 0; kk < 64; kk += 4) {
-    const double av = As[(kk + fk) * kGetrfLdA + 16 * wv + fr];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, Bs[(16 * u + fr) * kGetrfLdB + kk + fk], acc[u], 0, 0, 0);
-  }
-#pragma unroll
-  for (int u = 0; u < 4; ++u) {
-    const int c = 16 * u + fr;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int rr = 16 * wv + fk + 4 * q;
-      if (rr < mr && c < nc) Ab[(size_t)c * lda + rr] = acc[u][q];
-    }
-  }
-}
-
-size_t getrf_workspace_bytes(const GetrfDesc& g) {
-  const size_t nblk = (size_t)((g.n + 63) / 64);
-  return ((g.invL_out ? 0 : nblk) + (g.invU_out ? 0 : nblk)) * 4096 * sizeof(double);
-}
-
-void launch_getrf_nopiv(const GetrfDesc& g, hipStream_t stream, double* ws) {
-  if (g.n <= 0) return;
-  if (g.n > kTrsmMaxCols) fatal("dgetrf tile kernel: n=%d exceeds the tile limit %d", g.n, kTrsmMaxCols);
-  if (g.lda < g.n) fatal("dgetrf tile kernel: lda=%d < n=%d", g.lda, g.n);
-  const int nblk = (g.n + 63) / 64;
-  double* il = g.invL_out ? g.invL_out : ws;
-  double* iu = g.invU_out ? g.invU_out : ws + (g.invL_out ? 0 : (size_t)nblk * 4096);
-  for (int j = 0; j < g.n; j += 64) {
-    const int jb = std::min(64, g.n - j);
-    double* bl = il + (size_t)(j / 64) * 4096;
-    double* bu = iu + (size_t)(j / 64) * 4096;
-    hipLaunchKernelGGL(dgetrf_diag_kernel, dim3(1), dim3(256), 0, stream, g.A, g.lda, j, jb, bl, bu, g.info, g.info_base, t_launch_prio);
-    const int rest = g.n - j - jb;
-    if (rest <= 0) break;
-    const int nrb = (rest + 63) / 64;
-    hipLaunchKernelGGL(dgetrf_panel_kernel, dim3(2 * nrb), dim3(256), 0, stream, g.A, g.lda, g.n, j, (const double*)bl, (const double*)bu, nrb, t_launch_prio);
-    GemmDesc e{};
-    e.A = g.A + (size_t)j * g.lda + j + jb;
-    e.B = g.A + (size_t)(j + jb) * g.lda + j;
-    e.C = g.A + (size_t)(j + jb) * g.lda + j + jb;
-    e.m = rest; e.n = rest; e.k = jb;
-    e.lda = e.ldb = e.ldc = g.lda;
-    e.alpha = -1.0; e.beta = 1.0;
-    launch_gemm_batch(&e, 1, stream);
   }
 }
 
@@ -2005,14 +895,14 @@ size_t potrf_workspace_bytes(const PotrfDesc& p) {
 // L's 64x64 diagonal blocks by recursive doubling: groups of g blocks pair up,
 // inv([A 0; B C]) = [inv(A) 0; -inv(C) B inv(A)  inv(C)], each level two
 // grouped MFMA GEMMs over all pairs (log2(n/64) levels, no sequential solve).
-void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, double* ws);
-static void launch_lower_inverse(const double* L, int lda, int n, const double* invD, double* X, int ldx, double* tmp, hipStream_t stream) {
+
+void launch_lower_inverse(const double* L, int lda, int n, const double* invD, double* X, int ldx, double* tmp, hipStream_t stream) {
   const int nblk = (n + 63) / 64;
   (void)hipMemset2DAsync(X, (size_t)ldx * sizeof(double), 0, (size_t)n * sizeof(double), n, stream);
   for (int b0 = 0; b0 < nblk; b0 += kMaxCopyBatch) {
     CopyBatchArgs ca;
     ca.count = std::min(kMaxCopyBatch, nblk - b0);
-    ca.prio = t_launch_prio;
+    ca.prio = launch_settings().prio;
     ca.nscan = 0;
     ca.nunpack = 0;
     for (int i = 0; i < ca.count; ++i) {
@@ -2058,7 +948,7 @@ static void launch_lower_inverse(const double* L, int lda, int n, const double* 
 // Blocked tile Cholesky (lower). ws needs 4096 doubles unless p.invD_out keeps
 // every diagonal-block inverse (then the panel TRSMs can reuse them); with W_out
 // and no invD_out it needs every block inverse (potrf_workspace_bytes).
-void launch_trsm_inv(const TrsmDesc* descs, const double* const* invD, int n, hipStream_t stream, bool in_place);
+
 void launch_potrf(const PotrfDesc& p, hipStream_t stream, double* ws) {
   const int JB = 64;
   const bool keep_all = p.invD_out || p.W_out;
@@ -2090,219 +980,6 @@ void launch_potrf(const PotrfDesc& p, hipStream_t stream, double* ws) {
       hipLaunchKernelGGL(pack_upper_lt_kernel, dim3(nblk, nblk), dim3(256), 0, stream, p.W_out, p.ldw, p.A, p.lda, p.n);
     }
   }
-}
-
-// ============================ tile TRTRI, grouped TRMM (L^T B) and tile LAUUM
-// The inverse-with-the-Cholesky-factor kernels (DTRTRI / DLAUUM / DPOTRI). All
-// three take a lower triangular tile whose strict upper triangle belongs to
-// somebody else (the user's symmetric matrix keeps its upper half there): the
-// results never depend on it and it is never written.
-
-// dst's lower triangle := src's lower triangle (n x n); zero_upper also clears
-// dst's strict upper triangle (a workspace copy that GEMM-like kernels may read
-// as a full square). One workgroup per 64 x 64 block.
-__global__ __launch_bounds__(256) void copy_lower_kernel(const double* __restrict__ src, int lds, double* __restrict__ dst, int ldd, int n, int zero_upper) {
-  const int r0 = blockIdx.x * 64, c0 = blockIdx.y * 64;
-  if (c0 > r0 && !zero_upper) return;
-  const int r = r0 + (threadIdx.x & 63);
-  if (r >= n) return;
-  for (int cc = threadIdx.x >> 6; cc < 64; cc += 4) {
-    const int c = c0 + cc;
-    if (c >= n) break;
-    if (r >= c)
-      dst[(size_t)c * ldd + r] = src[(size_t)c * lds + r];
-    else if (zero_upper)
-      dst[(size_t)c * ldd + r] = 0.0;
-  }
-}
-
-// *info := info_base + the 1-based index of the first exactly-zero diagonal entry
-// of A (n x n), unless a smaller non-zero value is already there (GetrfDesc's rule)
-__global__ __launch_bounds__(256) void dtrtri_info_kernel(const double* __restrict__ A, int lda, int n, int* info, int info_base) {
-  __shared__ int bad_s;
-  if (threadIdx.x == 0) bad_s = 0x7fffffff;
-  __syncthreads();
-  int bad = 0x7fffffff;
-  for (int i = threadIdx.x; i < n; i += 256)
-    if (A[(size_t)i * lda + i] == 0.0) { bad = i + 1; break; }
-  if (bad != 0x7fffffff) atomicMin(&bad_s, bad);
-  __syncthreads();
-  if (threadIdx.x == 0 && bad_s != 0x7fffffff) {
-    const int val = info_base + bad_s;
-    const int old = atomicCAS(info, 0, val);
-    if (old != 0 && val < old) atomicMin(info, val);
-  }
-}
-
-size_t trtri_workspace_bytes(const TrtriDesc& t) {
-  const size_t inv = t.invD ? 0 : (size_t)((t.n + 63) / 64) * 4096;
-  const size_t tmp = (size_t)t.n * t.n / 2 + 4096;  // the doubling products of launch_lower_inverse
-  return (inv + (size_t)t.n * t.n + tmp) * sizeof(double);
-}
-
-// Tile TRTRI: the 64 x 64 diagonal-block inverses (dtrtri_diag_kernel, or the
-// caller's), then the block size doubles level by level, X21 = -X22 L21 X11 as
-// two grouped MFMA GEMMs over all pairs of a level (launch_lower_inverse). The
-// doubling runs in a clean n x n workspace square, because its products read
-// the X11 / X22 triangles as full squares (zeros above); the last kernel copies
-// the lower triangle to A (in place) or to W_out. L is read only before that
-// copy and only below its diagonal blocks, so in place needs no second buffer.
-void launch_trtri(const TrtriDesc& t, hipStream_t stream, double* ws) {
-  if (t.n <= 0) return;
-  if (t.n > kTrsmMaxCols) fatal("dtrtri tile kernel: n=%d exceeds the tile limit %d", t.n, kTrsmMaxCols);
-  if (t.lda < t.n || (t.W_out && t.ldw < t.n)) fatal("dtrtri tile kernel: leading dimension below n=%d", t.n);
-  const int nblk = (t.n + 63) / 64;
-  if (t.info) hipLaunchKernelGGL(dtrtri_info_kernel, dim3(1), dim3(256), 0, stream, (const double*)t.A, t.lda, t.n, t.info, t.info_base);
-  const double* inv = t.invD;
-  if (!inv) {
-    launch_trtri_diag(t.A, t.lda, t.n, ws, stream);
-    inv = ws;
-    ws += (size_t)nblk * 4096;
-  }
-  double* X = ws;
-  launch_lower_inverse(t.A, t.lda, t.n, inv, X, t.n, X + (size_t)t.n * t.n, stream);
-  hipLaunchKernelGGL(copy_lower_kernel, dim3(nblk, nblk), dim3(256), 0, stream, (const double*)X, t.n, t.W_out ? t.W_out : t.A, t.W_out ? t.ldw : t.lda, t.n, 0);
-}
-
-constexpr int kMaxTrmmBatch = 64;
-struct TrmmArgs {
-  int count;
-  int prio;
-  int block_start[kMaxTrmmBatch + 1];
-  TrmmDesc d[kMaxTrmmBatch];
-};
-static_assert(sizeof(TrmmArgs) <= 4096, "TrmmArgs exceeds the kernel argument limit");
-
-// B := alpha L^T B in place. Row block I of the result needs rows >= I of B
-// only, and a workgroup owns 16 columns of B: it loads its whole strip into LDS
-// ([row][16], rows zero-padded to a multiple of 16: the layout of
-// dtrsm_left_kernel, conflict-free MFMA B-operand reads), and only after the
-// barrier the waves write result rows back, so the in-place sweep never meets a
-// row it still needs. Wave w takes the 16-row blocks w, 15 - w, 16 + w, ... (the
-// work of a block shrinks linearly with its row, so the pairs even it out):
-// R_I = sum_{k >= I} L(k, I)^T B(k), v_mfma_f64_16x16x4f64 with L(k, I) read
-// from global memory (lane (fr, fk) feeds column I + fr, rows k + 4u + fk: every
-// element read lies on or below the diagonal, the diagonal 16 x 16 block is
-// masked, the ragged last k block is guarded).
-// TrmmDesc::lower: B is lower triangular (LAUUM): elements above its diagonal
-// are loaded as zero and not stored, and the row blocks above the strip's first
-// column are skipped. 66 VGPRs, no scratch: the waves fit beside a bulk GEMM
-// workgroup's; the strip takes n x 128 bytes of LDS (64 KB at n = 512).
-__global__ __launch_bounds__(kTrsmThreads) void dtrmm_lt_kernel(const TrmmArgs args) {
-  extern __shared__ double P[];  // [rows padded][16]
-  PARSEC_WAVE_PRIO(args.prio);
-  const int b = blockIdx.x;
-  const int di = find_desc(args, args.block_start, b);
-  const TrmmDesc& d = args.d[di];
-  const int j0 = (b - args.block_start[di]) * 16;
-  const int n = d.n, nrhs = d.nrhs;
-  const int nrb = (n + 15) / 16;
-  const bool lower = d.lower != 0;
-  const double alpha = d.alpha;
-  double* Bp = d.B;
-  const size_t ldb = d.ldb;
-  const double* __restrict__ L = d.L;
-  const size_t ldl = d.ldl;
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int fr = lane & 15, fk = lane >> 4;
-  for (int idx = tid; idx < nrb * 256; idx += kTrsmThreads) {
-    const int i = idx >> 4, c = j0 + (idx & 15);
-    P[idx] = (i < n && c < nrhs && (!lower || i >= c)) ? Bp[(size_t)c * ldb + i] : 0.0;
-  }
-  __syncthreads();
-  const int ib0 = lower ? j0 / 16 : 0;
-  for (int t = 0;; ++t) {
-    const int ib = ib0 + 8 * t + ((t & 1) ? 7 - wv : wv);
-    if (ib0 + 8 * t >= nrb) break;
-    if (ib >= nrb) continue;
-    const int i0 = ib * 16;
-    const int col = i0 + fr;  // column of L this lane feeds as the MFMA A-operand
-    const double* __restrict__ Lp = L + (size_t)min(col, n - 1) * ldl;
-    double4_t acc[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      // the diagonal block: only k >= column is L
-      const int kk = i0 + 4 * u + fk;
-      const double av = (kk >= col && kk < n) ? Lp[kk] : 0.0;
-      acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, P[kk * 16 + fr], (double4_t){0.0, 0.0, 0.0, 0.0}, 0, 0, 0);
-    }
-    int k = i0 + 16;
-    for (; k + 16 <= n; k += 16) {
-      double av[4], bv[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int kk = k + 4 * u + fk;
-        av[u] = Lp[kk];
-        bv[u] = P[kk * 16 + fr];
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u], bv[u], acc[u], 0, 0, 0);
-    }
-    if (k < n) {
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int kk = k + 4 * u + fk;
-        const double av = kk < n ? Lp[kk] : 0.0;
-        acc[u] = __builtin_amdgcn_mfma_f64_16x16x4f64(av, P[kk * 16 + fr], acc[u], 0, 0, 0);
-      }
-    }
-    const double4_t sum = acc[0] + acc[1] + acc[2] + acc[3];
-    const int c = j0 + fr;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int r = i0 + fk + 4 * q;
-      if (r < n && c < nrhs && (!lower || r >= c)) Bp[(size_t)c * ldb + r] = alpha * sum[q];
-    }
-  }
-}
-
-// One grouped launch per 64 descriptors, one workgroup per 16 columns of every B.
-void launch_trmm_lt_batch(const TrmmDesc* descs, int n, hipStream_t stream) {
-  if (n <= 0) return;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute((const void*)dtrmm_lt_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
-  for (int s0 = 0; s0 < n; s0 += kMaxTrmmBatch) {
-    const int cnt = std::min(kMaxTrmmBatch, n - s0);
-    TrmmArgs a;
-    a.count = cnt;
-    a.prio = t_launch_prio;
-    int total = 0, maxn = 0;
-    for (int i = 0; i < cnt; ++i) {
-      a.d[i] = descs[s0 + i];
-      a.block_start[i] = total;
-      if (a.d[i].n <= 0 || a.d[i].nrhs <= 0) continue;
-      if (a.d[i].ldl < a.d[i].n || a.d[i].ldb < a.d[i].n) fatal("dtrmm tile kernel: leading dimension below n=%d", a.d[i].n);
-      if (a.d[i].lower && a.d[i].nrhs != a.d[i].n) fatal("dtrmm tile kernel: a lower triangular B is square (n=%d, nrhs=%d)", a.d[i].n, a.d[i].nrhs);
-      total += (a.d[i].nrhs + 15) / 16;
-      maxn = std::max(maxn, a.d[i].n);
-    }
-    a.block_start[cnt] = total;
-    if (total == 0) continue;
-    if (maxn > kTrsmMaxCols) fatal("dtrmm tile kernel: n=%d exceeds the LDS-resident strip limit %d", maxn, kTrsmMaxCols);
-    const size_t lds = (size_t)((maxn + 15) / 16) * 256 * sizeof(double);
-    hipLaunchKernelGGL(dtrmm_lt_kernel, dim3(total), dim3(kTrsmThreads), lds, stream, a);
-  }
-}
-
-size_t lauum_workspace_bytes(const LauumDesc& l) { return (size_t)l.n * l.n * sizeof(double); }
-
-// Tile LAUUM, A := lower(L^T L) in place. Column strip J of the product reads
-// the columns >= J of L that other workgroups are overwriting at the same time.
-// The answer chosen here: the lower triangle of L is first copied to a workspace
-// square, and the grouped TRMM kernel then multiplies A's own lower triangle by
-// that copy's transpose (TrmmDesc::lower: lower-only load and store), so no
-// workgroup reads a location another one writes.
-void launch_lauum(const LauumDesc& l, hipStream_t stream, double* ws) {
-  if (l.n <= 0) return;
-  if (l.n > kTrsmMaxCols) fatal("dlauum tile kernel: n=%d exceeds the tile limit %d", l.n, kTrsmMaxCols);
-  if (l.lda < l.n) fatal("dlauum tile kernel: lda=%d < n=%d", l.lda, l.n);
-  const int nblk = (l.n + 63) / 64;
-  hipLaunchKernelGGL(copy_lower_kernel, dim3(nblk, nblk), dim3(256), 0, stream, (const double*)l.A, l.lda, ws, l.n, l.n, 1);
-  TrmmDesc t{ws, l.A, l.n, l.n, l.n, l.lda, 1.0, 1};
-  launch_trmm_lt_batch(&t, 1, stream);
 }
 
 // ====================================== tile POTRF (+W) in n/64 + 1 launches
@@ -2431,20 +1108,6 @@ __device__ __forceinline__ void acc_store(const double4_t (&acc)[2][2], double* 
       }
 }
 #undef PARSEC_ACC_MN
-
-// 16 x 16 x kn MFMA product into one accumulator tile: acc(m, n) += sign *
-// sum_k Sa[k][m] Sb[k][n] (LDS, leading dimensions lda_s / ldb_s, k from k0).
-// Lane layout of acc: m = lane & 15, n = (lane >> 4) + 4 q.
-__device__ __forceinline__ void mfma16(double4_t& acc, const double* Sa, int lda_s, const double* Sb, int ldb_s, int k0, int kn, double sign) {
-  const int lane = threadIdx.x & 63;
-  const int r = lane & 15, kq = lane >> 4;
-#pragma unroll
-  for (int kk = 0; kk < kn; kk += 4) {
-    const double y = Sa[(k0 + kk + kq) * lda_s + r];
-    const double x = sign * Sb[(k0 + kk + kq) * ldb_s + r];
-    acc = __builtin_amdgcn_mfma_f64_16x16x4f64(x, y, acc, 0, 0, 0);
-  }
-}
 
 // Factor the 64 x 64 SPD block held in LDS (Dl[c][r] = D(r, c), ld kPL) in
 // place and invert the factor: L (lower part) -> T (global, ldt), X = L^-1 ->
@@ -3077,130 +1740,6 @@ bool potrf_steps_eligible(const PotrfDesc& p) {
 
 size_t potrf_steps_workspace_bytes(const PotrfDesc& p) { return p.invD_out ? 0 : (size_t)(p.n / 64) * 4096 * sizeof(double); }
 
-// ---------------------------------------------- host-published panel estimates
-// Under PARSEC_DPOTRF_TRSM=auto the tile POTRF that writes W = L^-1 publishes
-// max|L| max|W| into pinned host memory when its last step launch retires. The
-// engine dispatches TRSM(m, k) only after POTRF(k)'s completion event, so the
-// TRSM launch reads the estimate on the host and launches the substitution
-// kernel only for the panels above the limit: no gated kernel rides the
-// critical stream behind every panel GEMM. A W whose estimate is unknown here
-// (factored by another process, or not yet published) takes the device-side
-// gate (scan in the copy kernel, in-place gated substitution kernel).
-namespace {
-constexpr uint32_t kEstSlots = 4096;
-struct EstimateSlots {
-  std::mutex m;
-  bool tried = false;
-  double* host = nullptr;              // [kEstSlots], pinned; 0 = not published
-  unsigned long long* dev = nullptr;   // [kEstSlots][4]: max|L|, max|W|, arrivals, pad
-  const double* owner[kEstSlots] = {};
-  uint32_t next = 0;
-  std::unordered_map<const double*, uint32_t> of_w;
-};
-EstimateSlots g_est[16];
-std::atomic<bool> g_est_any{false};  // some device has estimate slots (forget() is a no-op before)
-int g_est_route = -1;  // PARSEC_DPOTRF_TRSM_ESTIMATE: 1 = host-published (default), 0 = device gate only
-EstimateSlots* est_slots() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
-  return &g_est[dev];
-}
-}  // namespace
-
-int trsm_estimate_route(int on) {
-  if (g_est_route < 0) {
-    const char* e = getenv("PARSEC_DPOTRF_TRSM_ESTIMATE");
-    g_est_route = e ? (atoi(e) != 0) : 1;
-  }
-  const int prev = g_est_route;
-  if (on >= 0) g_est_route = on != 0;
-  return prev;
-}
-
-// A slot for the POTRF writing W (device / host halves), or false.
-static bool est_acquire(const double* W, unsigned long long** dev, double** host) {
-  if (trsm_estimate_route(-1) == 0 || parsec::trsm_inverse_mode(-1, 0.0) != 1) return false;
-  EstimateSlots* e = est_slots();
-  if (!e) return false;
-  std::lock_guard<std::mutex> lk(e->m);
-  if (!e->tried) {
-    e->tried = true;
-    void* h = nullptr;
-    void* d = nullptr;
-    if (hipHostMalloc(&h, kEstSlots * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) { (void)hipGetLastError(); h = nullptr; }
-    if (h && hipMalloc(&d, kEstSlots * 4 * sizeof(unsigned long long)) != hipSuccess) { (void)hipGetLastError(); d = nullptr; }
-    if (h && d && hipMemset(d, 0, kEstSlots * 4 * sizeof(unsigned long long)) == hipSuccess && hipDeviceSynchronize() == hipSuccess) {
-      std::memset(h, 0, kEstSlots * sizeof(double));
-      e->host = static_cast<double*>(h);
-      e->dev = static_cast<unsigned long long*>(d);
-      g_est_any.store(true, std::memory_order_release);
-    } else {
-      (void)hipGetLastError();
-      if (h) (void)hipHostFree(h);
-      if (d) (void)hipFree(d);
-    }
-  }
-  if (!e->host) return false;
-  const uint32_t slot = e->next++ % kEstSlots;
-  if (e->owner[slot]) {
-    auto it = e->of_w.find(e->owner[slot]);
-    if (it != e->of_w.end() && it->second == slot) e->of_w.erase(it);
-  }
-  e->owner[slot] = W;
-  e->of_w[W] = slot;
-  *reinterpret_cast<volatile double*>(&e->host[slot]) = 0.0;
-  *dev = e->dev + (size_t)slot * 4;
-  *host = e->host + slot;
-  return true;
-}
-
-// A device buffer was (re)allocated: whatever W it held is gone, so an estimate
-// keyed by its address must not be found for the next tile living there (a
-// receive buffer recycled from the pool or the zone, a tile re-staged after
-// eviction). Called by the zone allocator, device_alloc and the comm engine's
-// receive-buffer pool.
-void trsm_estimate_forget(const void* p) {
-  if (!p || !g_est_any.load(std::memory_order_acquire)) return;
-  for (EstimateSlots& e : g_est) {
-    std::lock_guard<std::mutex> lk(e.m);
-    if (!e.host) continue;
-    auto it = e.of_w.find(static_cast<const double*>(p));
-    if (it == e.of_w.end()) continue;
-    if (e.owner[it->second] == p) e.owner[it->second] = nullptr;
-    e.of_w.erase(it);
-  }
-}
-
-// The published estimate of the POTRF that wrote W (> 0), or 0 when unknown.
-static double est_lookup(const double* W) {
-  if (trsm_estimate_route(-1) == 0) return 0.0;
-  EstimateSlots* e = est_slots();
-  if (!e || !e->host) return 0.0;
-  std::lock_guard<std::mutex> lk(e->m);
-  auto it = e->of_w.find(W);
-  if (it == e->of_w.end() || e->owner[it->second] != W) return 0.0;
-  const double v = *reinterpret_cast<volatile const double*>(&e->host[it->second]);
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return v;
-}
-
-// tests: the estimate keyed by p on the current device, and every W address
-// holding a published one
-double trsm_estimate_lookup(const void* p) { return est_lookup(static_cast<const double*>(p)); }
-std::vector<uintptr_t> trsm_estimate_known() {
-  std::vector<uintptr_t> out;
-  EstimateSlots* e = est_slots();
-  if (!e) return out;
-  std::lock_guard<std::mutex> lk(e->m);
-  if (!e->host) return out;
-  for (const auto& kv : e->of_w)
-    if (e->owner[kv.second] == kv.first && *reinterpret_cast<volatile const double*>(&e->host[kv.second]) > 0.0) out.push_back((uintptr_t)kv.first);
-  return out;
-}
-
-// Estimates published / taken on the host / left to the device gate (tests, bench)
-static std::atomic<uint64_t> g_est_stats[3];
-
 void launch_potrf_steps(const PotrfDesc& p, hipStream_t stream, double* ws) {
   PotrfStepArgs a{};
   a.A = p.A; a.lda = p.lda; a.W = p.W_out; a.ldw = p.ldw; a.info = p.info;
@@ -3215,14 +1754,14 @@ void launch_potrf_steps(const PotrfDesc& p, hipStream_t stream, double* ws) {
     spread = e ? atoi(e) : 1;  // profiles/r3_potrf_spread_ab.txt
   }
   a.stamp = (g_potrf_stamp_mode ? 1 : 0) | (spread ? 2 : 0);
-  a.claim = t_launch_claim >= 1;
+  a.claim = launch_settings().claim >= 1;
   // PARSEC_POTRF_PACK=0 (measurement only): skip the L^T half of the packed
   // tile -- the substitution routes would then read garbage
   static const bool pack_env = !getenv("PARSEC_POTRF_PACK") || atoi(getenv("PARSEC_POTRF_PACK")) != 0;
   a.pack = p.pack_w && p.W_out && pack_env ? 1 : 0;
   a.est = nullptr;
   a.est_host = nullptr;
-  if (p.W_out && est_acquire(p.W_out, &a.est, &a.est_host)) g_est_stats[0].fetch_add(1, std::memory_order_relaxed);
+  if (p.W_out && trsm_estimate_acquire(p.W_out, &a.est, &a.est_host)) trsm_estimate_count(0);
   const int nb = p.n / 64;
   a.nb = nb;
   const bool w = p.W_out != nullptr;
@@ -3286,7 +1825,7 @@ size_t trsm_w_workspace_bytes(const TrsmGemmDesc* d, int n) {
 // grouped GEMM writes B from (copy x W^T). Panel-solve modes:
 //  * blocked: every panel with its factor by substitution (blocked TRSM with W's
 //    diagonal 64-blocks as the inverted diagonal blocks);
-//  * auto, estimate published by the local POTRF (est_lookup): the panels above
+//  * auto, estimate published by the local POTRF (trsm_estimate_lookup): the panels above
 //    the limit by substitution, the others through W -- decided here, no gate;
 //  * auto, estimate unknown (W from another process): the copy kernel estimates
 //    each W's conditioning (max|L| * max|W|) into workspace slots, the GEMM skips
@@ -3343,13 +1882,13 @@ void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, doubl
     if (mode == 2 && trsm_substitutable(t)) {
       route = 1;
     } else if (mode == 1 && trsm_substitutable(t)) {
-      const double e = est_lookup(t.W);
+      const double e = trsm_estimate_lookup(t.W);
       if (e > 0.0) {
         route = e > limit ? 1 : 0;
-        g_est_stats[1].fetch_add(1, std::memory_order_relaxed);
+        trsm_estimate_count(1);
       } else if (trsm_gateable(t)) {
         route = 2;
-        g_est_stats[2].fetch_add(1, std::memory_order_relaxed);
+        trsm_estimate_count(2);
       }
     }
     const int wix = info_of(t);
@@ -3417,7 +1956,7 @@ void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, doubl
          (via_w.empty() && (!pend_scan.empty() || !pend_unpack.empty()))) {
     CopyBatchArgs ca;
     ca.count = 0;
-    ca.prio = t_launch_prio;
+    ca.prio = launch_settings().prio;
     int maxc = 1;
     add_jobs(ca, maxc);
     if (ca.nscan + ca.nunpack > 0)
@@ -3430,7 +1969,7 @@ void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, doubl
     ca.count = 0;
     ca.nscan = 0;
     ca.nunpack = 0;
-    ca.prio = t_launch_prio;
+    ca.prio = launch_settings().prio;
     std::vector<GemmDesc> g(cnt);
     char* p = copies;
     int maxc = 1;
@@ -3487,336 +2026,10 @@ void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, doubl
   }
 }
 
-// counters: [0] estimates published by POTRF, [1] panel decisions taken on the
-// host, [2] panels left to the device gate
-void trsm_estimate_stats(uint64_t out[3], bool reset) {
-  for (int i = 0; i < 3; ++i) out[i] = reset ? g_est_stats[i].exchange(0) : g_est_stats[i].load();
-}
-
-}  // namespace kern
-
-namespace kern {
-size_t potrf_workspace_bytes(const PotrfDesc& p);
-size_t potrf_steps_workspace_bytes(const PotrfDesc& p);
-bool potrf_steps_eligible(const PotrfDesc& p);
-int potrf_steps_mode(int on);
-void launch_potrf_steps(const PotrfDesc& p, hipStream_t stream, double* ws);
-size_t trsm_w_workspace_bytes(const TrsmGemmDesc* d, int n);
-void launch_trsm_w_batch(const TrsmGemmDesc* d, int n, hipStream_t stream, double* ws);
-void launch_qr_panel(const QrPanelDesc* descs, int n, hipStream_t stream);
-void launch_stencil7_batch(const StencilDesc* d, int n, hipStream_t stream);
-void launch_qr_panel_blocked(const QrPanelDesc* descs, int n, hipStream_t stream, double* ws);
-size_t qr_panel_workspace_bytes(const QrPanelDesc* descs, int n);
-void launch_qr_apply(const QrApplyDesc* descs, int n, hipStream_t stream, double* ws);
-size_t qr_apply_workspace_bytes(const QrApplyDesc* descs, int n);
-}  // namespace kern
-
-size_t kernel_batch_workspace_bytes(const KernelBatch& b) {
-  size_t w = 0;
-  for (auto& p : b.potrf) w = std::max(w, kern::potrf_steps_eligible(p) ? kern::potrf_steps_workspace_bytes(p) : kern::potrf_workspace_bytes(p));
-  for (auto& g : b.getrf) w = std::max(w, kern::getrf_workspace_bytes(g));
-  if (!b.lu_panel.empty()) w = std::max(w, kern::lu_panel_workspace_bytes());
-  for (auto& t : b.trtri) w = std::max(w, kern::trtri_workspace_bytes(t));
-  for (auto& l : b.lauum) w = std::max(w, kern::lauum_workspace_bytes(l));
-  if (!b.trsm_w.empty()) w = std::max(w, kern::trsm_w_workspace_bytes(b.trsm_w.data(), (int)b.trsm_w.size()));
-  if (!b.qr_panel.empty()) w = std::max(w, kern::qr_panel_workspace_bytes(b.qr_panel.data(), (int)b.qr_panel.size()));
-  w = std::max(w, kern::trsm_workspace_bytes(b.trsm.data(), (int)b.trsm.size()));
-  w = std::max(w, kern::trsm_left_workspace_bytes(b.trsm_left.data(), (int)b.trsm_left.size()));
-  return std::max(w, kern::qr_apply_workspace_bytes(b.qr_apply.data(), (int)b.qr_apply.size()));
-}
-
-void launch_kernel_batch(KernelBatch& b, hipStream_t stream, int device_ordinal, void* ws) {
-  (void)device_ordinal;
-  struct PrioScope {
-    int prev, prev_pad, prev_claim, prev_yield;
-    PrioScope(bool on, int pad, int claim, bool yield)
-        : prev(kern::t_launch_prio), prev_pad(kern::t_launch_pad), prev_claim(kern::t_launch_claim), prev_yield(kern::t_launch_yield) {
-      kern::t_launch_prio = on ? 1 : 0;
-      kern::t_launch_pad = pad;
-      kern::t_launch_claim = claim;
-      kern::t_launch_yield = yield ? 1 : 0;
-    }
-    ~PrioScope() {
-      kern::t_launch_prio = prev;
-      kern::t_launch_pad = prev_pad;
-      kern::t_launch_claim = prev_claim;
-      kern::t_launch_yield = prev_yield;
-    }
-  } prio_scope(b.critical, b.one_per_cu ? kern::kBulkPadBytes : 0, b.claim_cus, b.bulk_yield);
-  // critical-path kernels first: a POTRF's fused update, POTRF, then TRSM, then the GEMM/SYRK updates
-  if (!b.pre_gemm.empty()) kern::launch_gemm_batch(b.pre_gemm.data(), (int)b.pre_gemm.size(), stream);
-  for (auto& p : b.potrf) {
-    if (kern::potrf_steps_eligible(p)) kern::launch_potrf_steps(p, stream, static_cast<double*>(ws));
-    else kern::launch_potrf(p, stream, static_cast<double*>(ws));
-  }
-  for (auto& g : b.getrf) kern::launch_getrf_nopiv(g, stream, static_cast<double*>(ws));
-  for (auto& g : b.lu_panel) kern::launch_lu_panel(g, stream, static_cast<double*>(ws), kern::t_launch_prio);
-  if (!b.qr_panel.empty()) kern::launch_qr_panel_blocked(b.qr_panel.data(), (int)b.qr_panel.size(), stream, static_cast<double*>(ws));
-  if (!b.trsm.empty()) kern::launch_trsm_batch(b.trsm.data(), (int)b.trsm.size(), stream, static_cast<double*>(ws));
-  if (!b.trsm_w.empty()) kern::launch_trsm_w_batch(b.trsm_w.data(), (int)b.trsm_w.size(), stream, static_cast<double*>(ws));
-  // GESSM / SSSSM: the interchanges, then the unit lower solves; their updates are GEMMs
-  if (!b.laswp.empty()) kern::launch_laswp_batch(b.laswp.data(), (int)b.laswp.size(), stream, kern::t_launch_prio);
-  if (!b.trsm_left.empty()) kern::launch_trsm_left_batch(b.trsm_left.data(), (int)b.trsm_left.size(), stream, static_cast<double*>(ws));
-  if (!b.qr_apply.empty()) kern::launch_qr_apply(b.qr_apply.data(), (int)b.qr_apply.size(), stream, static_cast<double*>(ws));
-  // the inverse kernels (DTRTRI / DLAUUM): a round's TRMMs are one grouped launch
-  for (auto& t : b.trtri) kern::launch_trtri(t, stream, static_cast<double*>(ws));
-  if (!b.trmm.empty()) kern::launch_trmm_lt_batch(b.trmm.data(), (int)b.trmm.size(), stream);
-  for (auto& l : b.lauum) kern::launch_lauum(l, stream, static_cast<double*>(ws));
-  if (!b.gemm.empty()) kern::launch_gemm_batch(b.gemm.data(), (int)b.gemm.size(), stream);
-  if (!b.stencil.empty()) kern::launch_stencil7_batch(b.stencil.data(), (int)b.stencil.size(), stream);
-  for (auto& g : b.generic) g(stream);
-}
-
-// Device-to-device byte copy as a kernel (16-byte vectors, grid-stride): used for
-// pulls from peer-process (IPC) allocations so the copy is an ordinary kernel in
-// stream order on this process's queue.
-__global__ __launch_bounds__(256) void copy_bytes_kernel(uint4* __restrict__ dst, const uint4* __restrict__ src, size_t n16) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) dst[i] = src[i];
-}
-__global__ void copy_tail_kernel(char* __restrict__ dst, const char* __restrict__ src, size_t n) {
-  for (size_t i = threadIdx.x; i < n; i += blockDim.x) dst[i] = src[i];
-}
-
-int device_copy_kernel(void* dst, const void* src, size_t bytes, void* stream) {
-  hipStream_t s = (hipStream_t)stream;
-  const bool aligned = ((uintptr_t)dst % 16 == 0) && ((uintptr_t)src % 16 == 0);
-  size_t n16 = aligned ? bytes / 16 : 0;
-  if (n16) {
-    const unsigned blocks = (unsigned)std::min<size_t>(1024, (n16 + 255) / 256);
-    hipLaunchKernelGGL(copy_bytes_kernel, dim3(blocks), dim3(256), 0, s, static_cast<uint4*>(dst), static_cast<const uint4*>(src), n16);
-  }
-  const size_t done = n16 * 16;
-  if (bytes > done) hipLaunchKernelGGL(copy_tail_kernel, dim3(1), dim3(256), 0, s, static_cast<char*>(dst) + done, static_cast<const char*>(src) + done, bytes - done);
-  return (int)hipGetLastError();
-}
-
-// Multi-source gather: ONE launch moves up to kMaxGather transfers, each from
-// another peer's IPC mapping. Across xGMI every peer GPU sits behind its own
-// link, so the transfers of one launch pull over up to 7 links at once while
-// the process keeps one copy stream (one hardware queue). Workgroups are split
-// between the transfers in proportion to their size (at most 64 per transfer,
-// 4 x 16-byte loads in flight per thread: ~1 MiB in flight per link).
-constexpr int kMaxGather = 16;
-struct GatherArgs {
-  int count;
-  int wg_start[kMaxGather + 1];
-  uint4* dst[kMaxGather];
-  const uint4* src[kMaxGather];
-  unsigned long long n16[kMaxGather];
-};
-static_assert(sizeof(GatherArgs) <= 4096, "GatherArgs exceeds the kernel argument limit");
-__global__ __launch_bounds__(256) void gather_kernel(const GatherArgs a) {
-  int t = 0;
-  while (t + 1 < a.count && (int)blockIdx.x >= a.wg_start[t + 1]) ++t;
-  const int w = (int)blockIdx.x - a.wg_start[t], nw = a.wg_start[t + 1] - a.wg_start[t];
-  uint4* __restrict__ d = a.dst[t];
-  const uint4* __restrict__ s = a.src[t];
-  const size_t n = a.n16[t], stride = (size_t)nw * 256;
-  size_t i = (size_t)w * 256 + threadIdx.x;
-  for (; i + 3 * stride < n; i += 4 * stride) {
-    const uint4 v0 = s[i], v1 = s[i + stride], v2 = s[i + 2 * stride], v3 = s[i + 3 * stride];
-    d[i] = v0;
-    d[i + stride] = v1;
-    d[i + 2 * stride] = v2;
-    d[i + 3 * stride] = v3;
-  }
-  for (; i < n; i += stride) d[i] = s[i];
-}
-
-int device_gather_kernel(void* const* dst, const void* const* src, const size_t* bytes, int n, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  for (int i = 0; i < n;) {
-    GatherArgs a{};
-    int wg = 0;
-    for (; i < n && a.count < kMaxGather; ++i) {
-      const bool aligned = ((uintptr_t)dst[i] % 16 == 0) && ((uintptr_t)src[i] % 16 == 0) && bytes[i] % 16 == 0;
-      if (!aligned || bytes[i] == 0) {  // odd sizes / offsets: a copy kernel of its own, same stream
-        if (bytes[i] && device_copy_kernel(dst[i], src[i], bytes[i], stream) != 0) return -1;
-        continue;
-      }
-      const int k = a.count++;
-      a.dst[k] = static_cast<uint4*>(dst[i]);
-      a.src[k] = static_cast<const uint4*>(src[i]);
-      a.n16[k] = bytes[i] / 16;
-      a.wg_start[k] = wg;
-      wg += (int)std::min<size_t>(64, std::max<size_t>(1, a.n16[k] / (256 * 16)));
-    }
-    if (!a.count) continue;
-    a.wg_start[a.count] = wg;
-    hipLaunchKernelGGL(gather_kernel, dim3(wg), dim3(256), 0, st, a);
-  }
-  return (int)hipGetLastError();
-}
-
-// Panel-solve mode of the tile Cholesky (device.hpp trsm_inverse_mode).
-// PARSEC_DPOTRF_TRSM = inverse | auto | blocked, PARSEC_DPOTRF_TRSM_LIMIT = the
-// estimate above which auto solves by substitution (scripts/trsm_inverse_numerics.py,
-// profiles/r4_trsm_inverse_numerics.txt).
-static std::atomic<int> g_trsm_mode{-1};
-static std::atomic<double> g_trsm_limit{0.0};
-static void trsm_mode_init() {
-  static std::once_flag once;
-  std::call_once(once, [] {
-    int m = 1;
-    if (const char* e = getenv("PARSEC_DPOTRF_TRSM")) m = !strcmp(e, "inverse") ? 0 : !strcmp(e, "blocked") ? 2 : 1;
-    double lim = 1e6;
-    if (const char* e = getenv("PARSEC_DPOTRF_TRSM_LIMIT")) lim = atof(e);
-    int exp = -1;
-    g_trsm_mode.compare_exchange_strong(exp, m);
-    double z = 0.0;
-    g_trsm_limit.compare_exchange_strong(z, lim > 0 ? lim : 1e6);
-  });
-}
-int trsm_inverse_mode(int mode, double limit) {
-  trsm_mode_init();
-  const int prev = g_trsm_mode.load();
-  if (mode >= 0) g_trsm_mode.store(mode);
-  if (limit > 0) g_trsm_limit.store(limit);
-  return prev;
-}
-double trsm_inverse_limit() {
-  trsm_mode_init();
-  return g_trsm_limit.load(std::memory_order_relaxed);
-}
-
-}  // namespace parsec
-
-// ------------------------------------------------- C entry points (tests/bench)
-namespace {
-std::mutex g_ws_m;
-void* g_ws = nullptr;
-size_t g_ws_bytes = 0;
-void* test_ws(size_t bytes) {
-  std::lock_guard<std::mutex> g(g_ws_m);
-  if (g_ws_bytes < bytes) {
-    (void)hipDeviceSynchronize();
-    if (g_ws) (void)hipFree(g_ws);
-    (void)hipMalloc(&g_ws, bytes);
-    g_ws_bytes = bytes;
-  }
-  return g_ws;
-}
-}  // namespace
-
-extern "C" {
-int parsec_amd_gemm_tile_policy(int p) { return parsec::kern::gemm_tile_policy(p); }
-int parsec_amd_gemm_splitk(int on) { return parsec::kern::gemm_splitk(on); }
-int parsec_amd_gemm_mainloop(int mode) { return parsec::kern::gemm_mainloop(mode); }
-int parsec_amd_gemm_pipeline(int mode) { return parsec::kern::gemm_pipeline(mode); }
-int parsec_amd_dgemm_batch(const parsec::GemmDesc* descs, int n, void* stream) {
-  // PARSEC_GEMM_PAD_TEST=1: launch like a DPOTRF bulk stream (padded LDS: one
-  // 128x128 workgroup per CU) -- kernel benchmarks of the in-DAG regime
-  const int prev = parsec::kern::t_launch_pad;
-  if (parsec::kern::gemm_policy().pad_test) parsec::kern::t_launch_pad = parsec::kern::kBulkPadBytes;
-  parsec::kern::launch_gemm_batch(descs, n, (hipStream_t)stream);
-  parsec::kern::t_launch_pad = prev;
-  return (int)hipGetLastError();
-}
-// Test hook, like PARSEC_GEMM_PAD_TEST above and not part of the public
-// interface (include/parsec.h): the same launch as a bulk stream of an engine
-// with cu_yield on issues it, i.e. the workgroups poll their CU's claim count
-// once per k-tile (tests/test_gemm_pipeline_gpu.py)
-int parsec_amd_dgemm_batch_yield(const parsec::GemmDesc* descs, int n, void* stream) {
-  const int prev = parsec::kern::t_launch_yield;
-  parsec::kern::t_launch_yield = 1;
-  const int rc = parsec_amd_dgemm_batch(descs, n, stream);
-  parsec::kern::t_launch_yield = prev;
-  return rc;
-}
-// BLAS-style single DGEMM, C = alpha op(A) op(B) + beta C, column major, on
-// `stream` (the signature a BODY dyld= or a DTD chore calls; reference
-// stress.jdf resolves cublasDgemm the same way). Returns a hipError_t.
-int parsec_amd_dgemm(char transa, char transb, int m, int n, int k, double alpha, const double* A, int lda, const double* B, int ldb, double beta,
-                     double* C, int ldc, void* stream) {
-  parsec::GemmDesc d{};
-  d.A = A; d.B = B; d.C = C;
-  d.m = m; d.n = n; d.k = k;
-  d.lda = lda; d.ldb = ldb; d.ldc = ldc;
-  d.alpha = alpha; d.beta = beta;
-  d.transA = (transa == 'T' || transa == 't' || transa == 'C' || transa == 'c');
-  d.transB = (transb == 'T' || transb == 't' || transb == 'C' || transb == 'c');
-  if (m <= 0 || n <= 0) return 0;
-  return parsec_amd_dgemm_batch(&d, 1, stream);
-}
-int parsec_amd_dtrsm_batch(const parsec::TrsmDesc* descs, int n, void* stream) {
-  void* ws = test_ws(parsec::kern::trsm_workspace_bytes(descs, n) + 64);
-  parsec::kern::launch_trsm_batch(descs, n, (hipStream_t)stream, static_cast<double*>(ws));
-  return (int)hipGetLastError();
-}
-// B := alpha op(L)^-1 B for a batch; descriptors without invD get their
-// diagonal-block inverses computed into cached scratch
-int parsec_amd_dtrsm_left_batch(const parsec::TrsmLeftDesc* descs, int n, void* stream) {
-  void* ws = test_ws(parsec::kern::trsm_left_workspace_bytes(descs, n) + 64);
-  parsec::kern::launch_trsm_left_batch(descs, n, (hipStream_t)stream, static_cast<double*>(ws));
-  return (int)hipGetLastError();
-}
-int parsec_amd_dpotrf_tile(double* A, int n, int lda, int* info, void* stream) {
-  parsec::PotrfDesc p{A, n, lda, info};
-  if (parsec::kern::potrf_steps_eligible(p)) {
-    void* ws = test_ws(parsec::kern::potrf_steps_workspace_bytes(p) + 64);
-    parsec::kern::launch_potrf_steps(p, (hipStream_t)stream, static_cast<double*>(ws));
-    return (int)hipGetLastError();
-  }
-  void* ws = test_ws(4096 * sizeof(double));
-  parsec::kern::launch_potrf(p, (hipStream_t)stream, static_cast<double*>(ws));
-  return (int)hipGetLastError();
-}
-// Tile LU without pivoting; invL / invU (optional) receive the diagonal-block inverses
-int parsec_amd_dgetrf_nopiv_tile(double* A, int n, int lda, int* info, double* invL, double* invU, void* stream) {
-  parsec::GetrfDesc g{A, n, lda, info, invL, invU};
-  void* ws = test_ws(parsec::kern::getrf_workspace_bytes(g) + 64);
-  parsec::kern::launch_getrf_nopiv(g, (hipStream_t)stream, static_cast<double*>(ws));
-  return (int)hipGetLastError();
-}
-// Tile TRTRI (lower, non-unit): A := L^-1 in place, or W (ld ldw) := L^-1
-int parsec_amd_dtrtri_tile(double* A, int n, int lda, int* info, int info_base, double* W, int ldw, void* stream) {
-  parsec::TrtriDesc t{A, n, lda, info, info_base, W, ldw, nullptr};
-  void* ws = test_ws(parsec::kern::trtri_workspace_bytes(t) + 64);
-  parsec::kern::launch_trtri(t, (hipStream_t)stream, static_cast<double*>(ws));
-  return (int)hipGetLastError();
-}
-// B := alpha L^T B for a batch, one grouped launch
-int parsec_amd_dtrmm_lt_batch(const parsec::TrmmDesc* descs, int n, void* stream) {
-  parsec::kern::launch_trmm_lt_batch(descs, n, (hipStream_t)stream);
-  return (int)hipGetLastError();
-}
-// Tile LAUUM: A := lower(L^T L) in place
-int parsec_amd_dlauum_tile(double* A, int n, int lda, void* stream) {
-  parsec::LauumDesc l{A, n, lda};
-  void* ws = test_ws(parsec::kern::lauum_workspace_bytes(l) + 64);
-  parsec::kern::launch_lauum(l, (hipStream_t)stream, static_cast<double*>(ws));
-  return (int)hipGetLastError();
-}
-// Tile Cholesky that also writes W = L^-1 (ld ldw)
-int parsec_amd_dpotrf_tile_w(double* A, int n, int lda, int* info, double* W, int ldw, void* stream, int pack) {
-  parsec::PotrfDesc p{A, n, lda, info};
-  p.W_out = W;
-  p.ldw = ldw;
-  p.pack_w = pack ? 1 : 0;
-  if (parsec::kern::potrf_steps_eligible(p)) {
-    void* ws = test_ws(parsec::kern::potrf_steps_workspace_bytes(p) + 64);
-    parsec::kern::launch_potrf_steps(p, (hipStream_t)stream, static_cast<double*>(ws));
-    return (int)hipGetLastError();
-  }
-  void* ws = test_ws(parsec::kern::potrf_workspace_bytes(p));
-  parsec::kern::launch_potrf(p, (hipStream_t)stream, static_cast<double*>(ws));
-  return (int)hipGetLastError();
-}
 // Phase clocks of the last stamped diagonal factorization (PARSEC_POTRF_STAMPS=1)
-int parsec_amd_potrf_stamps(long long* out) {
-  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(parsec::kern::g_potrf_stamps), sizeof(long long) * 16, 0, hipMemcpyDeviceToHost);
+int potrf_stamps_read(long long* out) {
+  return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_potrf_stamps), sizeof(long long) * 16, 0, hipMemcpyDeviceToHost);
 }
-// Select the tile POTRF: 1 = n/64 + 1 fused step launches (default), 0 = the
-// 3-launches-per-64-columns path; < 0 queries. Returns the previous setting.
-int parsec_amd_potrf_steps(int on) {
-  parsec::kern::potrf_steps_eligible(parsec::PotrfDesc{nullptr, 0, 0, nullptr});
-  const int prev = parsec::kern::potrf_steps_mode(on);
-  return prev;
-}
-// B := B W^T for a batch (the DPOTRF panel solve through the inverse)
-int parsec_amd_trsm_w_batch(const parsec::TrsmGemmDesc* d, int n, void* stream) {
-  void* ws = test_ws(parsec::kern::trsm_w_workspace_bytes(d, n) + 64);
-  parsec::kern::launch_trsm_w_batch(d, n, (hipStream_t)stream, static_cast<double*>(ws));
-  return (int)hipGetLastError();
-}
-}
+
+}  // namespace kern
+}  // namespace parsec

@@ -17,39 +17,13 @@
 #include "../device/device.hpp"
 #include "../device/hip_device.hpp"
 #include "../dtd/dtd.hpp"
+#include "../kernels/kernels.hpp"
 #include "../prof/profiling.hpp"
 #include "../ptg/ptg.hpp"
 
 namespace py = pybind11;
 using namespace parsec;
 
-extern "C" int parsec_amd_dgemm_batch(const GemmDesc* descs, int n, void* stream);
-extern "C" int parsec_amd_dgemm(char transa, char transb, int m, int n, int k, double alpha, const double* A, int lda, const double* B, int ldb, double beta,
-                                double* C, int ldc, void* stream);
-extern "C" int parsec_amd_gemm_tile_policy(int p);
-extern "C" int parsec_amd_gemm_splitk(int on);
-extern "C" int parsec_amd_gemm_mainloop(int mode);
-extern "C" int parsec_amd_gemm_pipeline(int mode);
-extern "C" int parsec_amd_dgemm_batch_yield(const parsec::GemmDesc* descs, int n, void* stream);
-extern "C" int parsec_amd_potrf_steps(int on);
-extern "C" int parsec_amd_potrf_stamps(long long* out);
-extern "C" int parsec_amd_dtrsm_batch(const TrsmDesc* descs, int n, void* stream);
-extern "C" int parsec_amd_dtrsm_left_batch(const TrsmLeftDesc* descs, int n, void* stream);
-extern "C" int parsec_amd_dgetrf_nopiv_tile(double* A, int n, int lda, int* info, double* invL, double* invU, void* stream);
-extern "C" int parsec_amd_dgetrf_piv_tile(double* A, int n, int lda, double* L, int ldl, int* info, void* stream);
-extern "C" int parsec_amd_dtstrf_tile(double* U, int ldu, double* A2, int lda2, int h, int n, double* L, int ldl, int* info, void* stream);
-extern "C" int parsec_amd_dlaswp_pair(double* top, int ldt, int mt, double* bot, int ldb, int h, int ncols, const double* piv, int npiv, void* stream);
-extern "C" int parsec_amd_dtrtri_tile(double* A, int n, int lda, int* info, int info_base, double* W, int ldw, void* stream);
-extern "C" int parsec_amd_dtrmm_lt_batch(const parsec::TrmmDesc* descs, int n, void* stream);
-extern "C" int parsec_amd_dlauum_tile(double* A, int n, int lda, void* stream);
-extern "C" int parsec_amd_dpotrf_tile(double* A, int n, int lda, int* info, void* stream);
-extern "C" int parsec_amd_trsm_w_batch(const parsec::TrsmGemmDesc* d, int n, void* stream);
-extern "C" int parsec_amd_dpotrf_tile_w(double* A, int n, int lda, int* info, double* W, int ldw, void* stream, int pack);
-extern "C" int parsec_amd_qr_panel(const parsec::QrPanelDesc* d, int n, void* stream);
-extern "C" int parsec_amd_qr_profile(unsigned long long* out);
-extern "C" int parsec_amd_qr_apply(const parsec::QrApplyDesc* d, int n, void* ws, void* stream);
-extern "C" size_t parsec_amd_qr_apply_ws(const parsec::QrApplyDesc* d, int n);
-extern "C" int parsec_amd_qr_extract_v(const double* A, int lda, int rows, int cols, double* Vout, void* stream);
 namespace parsec { void register_builtin_dtd_gpu_bodies(); std::function<int(GpuExecContext*, Task*)> builtin_dtd_gpu_body(const std::string& name); }
 
 namespace {

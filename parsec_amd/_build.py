@@ -35,6 +35,11 @@ CORE_SOURCES = [
     "csrc/data/collections.cpp",
     "csrc/device/device.cpp",
     "csrc/device/hip_device.cpp",
+    # host-only parts of the kernel layer (instrumented in the --sanitize builds)
+    "csrc/kernels/gemm_plan.cpp",
+    "csrc/kernels/trsm_estimate.cpp",
+    "csrc/kernels/kernel_batch.cpp",
+    "csrc/kernels/kernel_capi.cpp",
     "csrc/prof/profiling.cpp",
     "csrc/prof/ptg_to_dtd.cpp",
     "csrc/comm/remote_dep.cpp",
@@ -61,6 +66,9 @@ CORE_SOURCES = [
 ]
 HIP_SOURCES = [
     "csrc/kernels/tile_kernels.hip",
+    "csrc/kernels/trsm_kernels.hip",
+    "csrc/kernels/inverse_kernels.hip",
+    "csrc/kernels/copy_kernels.hip",
     "csrc/kernels/qr_kernels.hip",
     "csrc/kernels/lu_kernels.hip",
     "csrc/kernels/stencil_kernels.hip",

@@ -2,7 +2,7 @@
 against fp64 torch references:
 
 * the grouped 128x128 8-wave DGEMM in its FULL / C-preload form (selected only
-  when a launch holds >= 384 128-tiles: tile_kernels.hip launch_gemm_chunk), for
+  when a launch holds >= 384 128-tiles: csrc/kernels/gemm_plan.cpp gemm_plan_launch), for
   the GEMM (NT, alpha=-1, beta=1) and lower-only SYRK descriptors DPOTRF emits;
 * tiled DPOTRF at nb=1024 (grouped batches of >= 384 tiles) on an
   ill-conditioned SPD matrix A = Q diag(lambda) Q^T, cond(A) = 1e10, not
